@@ -14,10 +14,12 @@ config/cfg_nlst.yaml:71). Workload = BASELINE.json configs[1]: ABMIL generator +
 discriminator on synthetic 8192-patch x 1024 bags, resident in HBM before the timed region
 (>= 64 distinct bags per GPU = 2.1 GB >> the 256 MB Infinity Cache). Multi-GPU: bag-parallel, every rank
 runs its own bags, one RCCL all-reduce of each network's flat gradient arena per step. `value` is the WEAK-scaling figure
-(global step batch = bags x N); the line also carries `strong_scaling` (N > 1): the reference's own step batch of 16 bags
+(global step batch = bags x N); under --full the line also carries `strong_scaling` (N > 1): the reference's own step batch of 16 bags
 (cfg_nlst.yaml:71) split over the ranks, 16 / N bags per rank per step.
 
-Prints ONE JSON line (rank 0). Extra objects:
+A plain run sets up, warms up, times the --steps steps, writes the last step's outputs (--dump-outputs DIR: DIR/<name>.npy, rank 0)
+and prints ONE JSON line (rank 0): `value`, `ms_per_step` and the configuration. Everything else it can measure or check runs only
+under --full and fills these objects of the line (null otherwise):
   roofline     : the dominant kernel of the step. ABMIL / DeepAttMISL / PatchGCN: the contraction (kernel, shape) that owns the
                  most device time in an instrumented pass (HIP events around every launch on the launch stream), then timed as 50
                  back-to-back launches; algorithmic 2MNK flops / duration against the MFMA roof of the arithmetic mode.
@@ -71,6 +73,11 @@ def parse():
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--no-strong", action="store_true", help="skip the strong-scaling leg (N > 1)")
     ap.add_argument("--cpu-bags", type=int, default=16, help="bags per optimizer step of the CPU-baseline sample (16 = the GPU line's step batch)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every measurement and check beyond the headline (rooflines, extras, product loop, CPU baseline, "
+                         "strong scaling, per-rank times, replica and loss checks); the --no-* options above trim this set")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step computed (predictions, scores, losses, weights after the update) as DIR/<name>.npy")
     return ap.parse_args()
 
 
@@ -217,8 +224,10 @@ class Case:
         self.cursor = (i0 + nb) % self.n_pool
         bx, by, bh = [self.xs[i] for i in idx], [self.ys[i] for i in idx], [self.ys_host[i] for i in idx]
         plan = h._plan(bx, by, "wlabel", None, bh)
-        h._update_disc(0, bx, by, "wlabel", None, ys_host=bh, plan=plan)
+        n_logs = len(h.history)
+        preds, fakes = h._update_disc(0, bx, by, "wlabel", None, ys_host=bh, plan=plan)
         h._update_gen(0, bx, by, "wlabel", None, ys_host=bh, plan=plan)
+        self.last_out = (preds, fakes, h.history[n_logs:])
         h.rng.advance(1)
         if len(h.history) > 64:
             h.history.clear()
@@ -243,6 +252,27 @@ class Case:
         t_submit = time.perf_counter() - t0     # host time to enqueue all K steps (== dt when the host is the bottleneck)
         barrier()
         return time.perf_counter() - t0, t_submit
+
+    def dump_outputs(self, out_dir):
+        """What the last step handed its caller, as out_dir/<name>.npy: the per-bag predictions (y_hat) and discriminator scores of the fakes
+        (f_fake), both networks' flat parameters after the step's Adam updates (weights_G, weights_D), all float32, and every logged
+        loss / statistic of the step under its log name (float64 scalars). Same arguments -> same bags, weights and draws."""
+        import numpy as np
+        h = self.h
+        if self.graphs:
+            g = self.graphs[(self.cursor - 1) % len(self.graphs)]
+            preds, fakes, logs = g.preds, g.fakes, g.logs
+        else:
+            preds, fakes, logs = self.last_out
+        os.makedirs(out_dir, exist_ok=True)
+        arrays = {"y_hat": self.torch.cat(preds), "f_fake": self.torch.cat(fakes),
+                  "weights_G": h.optimizerG.flat_param, "weights_D": h.optimizerD.flat_param}
+        for name, t in arrays.items():
+            np.save(os.path.join(out_dir, name + ".npy"), t.detach().float().cpu().numpy())
+        for d in logs:
+            for k, v in h.resolve_log(d).items():
+                if k != "i_batch":
+                    np.save(os.path.join(out_dir, k.split("/")[-1] + ".npy"), np.float64(v))
 
     def logs_finite(self):
         h = self.h
@@ -787,6 +817,8 @@ def main():
     args = parse()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         return self_launch(args)
+    if not args.full:                      # a plain run times the headline step and nothing else
+        args.no_extras = args.no_roofline = args.no_cpu_baseline = args.no_strong = True
     import torch
     import torch.distributed as dist
     from advmil_amd import ops, parallel
@@ -850,14 +882,17 @@ def main():
     dt, t_submit = case.timed(args.steps, args.warmup, barrier)
     multi = None
     if world > 1:
-        multi = {"per_rank_ms_per_step": [round(1e3 * v / args.steps, 4) for v in per_rank(dt)],
+        multi = {"per_rank_ms_per_step": [round(1e3 * v / args.steps, 4) for v in per_rank(dt)] if args.full else None,
                  "collectives_in_graph": bool(case.graphs and case.graphs[0].captured_collectives)}
         t = torch.tensor([dt], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
-        multi["exposed_allreduce"] = exposed_allreduce(case)
+    if args.dump_outputs and rank == 0:    # before any leg below runs more steps through the same handler
+        case.dump_outputs(args.dump_outputs)
+    if world > 1:
+        multi["exposed_allreduce"] = exposed_allreduce(case) if args.full else None
         beat("weak leg done")
-    finite = case.logs_finite()
+    finite = case.logs_finite() if args.full else None
 
     # ---- strong scaling (N > 1): the reference's own optimizer step of 16 bags (cfg_nlst.yaml:71) split over the ranks, bag i of
     # the step batch on rank i mod W -> 16 / W bags per rank per step; same barrier / max-over-ranks timing
@@ -893,8 +928,8 @@ def main():
             strong = {"skipped": f"16 bags per step do not divide over {world} ranks"}
 
     # replicas must hold bit-identical weights after the timed steps (same reduced gradients, same Adam)
-    in_sync = True
-    if world > 1:
+    in_sync = True if args.full else None
+    if world > 1 and args.full:
         # everything from here to the final barrier is untimed bookkeeping: the instrumented eager pass on every rank, then rank 0's own
         # roofline / cpu_baseline / extras legs (minutes) while the other ranks wait in the barrier -> the long leash again
         beat("timed legs done: roofline + extras", setup=True)
@@ -1179,7 +1214,7 @@ def main():
                        "bags_per_step_per_gpu": args.bags, "global_bags_per_step": args.bags * world, "gen_updates": 1,
                        "distinct_resident_bags_per_gpu": case.n_pool, "parallelism": f"bag-parallel dp{world}", "dropout": "shipped rates",
                        "launch": case.launch_note},
-            "gd_steps_per_sec": round(args.steps / dt, 3), "losses_finite": bool(finite), "replicas_in_sync": in_sync,
+            "gd_steps_per_sec": round(args.steps / dt, 3), "losses_finite": finite, "replicas_in_sync": in_sync,
             "host_submit_ms_per_step": round(1e3 * t_submit / args.steps, 3),
             "roofline": roof, "gemm_roofline": (gemm_roof if roof is not gemm_roof else None), "pool_roofline": pool_roof,
             "cpu_baseline": cpu, "exact_f32_mfma_mode": exact_extra, "bp_every_batch_1": bp1_extra, "sizes": sizes,

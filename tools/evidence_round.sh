@@ -6,6 +6,6 @@ O=${1:-gpurun_out/evidence_r06}
 mkdir -p $O
 echo "commit $(cat .commit_hash 2>/dev/null || echo unknown)  $(date -u +%Y-%m-%dT%H:%MZ)" > $O/commit.txt
 timeout 1500 python -m pytest tests -m gpu -x -q > $O/gpu_suite.log 2>&1; tail -3 $O/gpu_suite.log
-timeout 900 python bench.py > $O/bench_line_abmil8k.json 2> $O/bench_line_abmil8k.err; tail -c 300 $O/bench_line_abmil8k.json; echo
-timeout 600 python bench.py --mode patch --patches 32768 --pool 16 --steps 20 --no-extras > $O/bench_line_esat32k.json 2> $O/bench_line_esat32k.err
+timeout 900 python bench.py --full > $O/bench_line_abmil8k.json 2> $O/bench_line_abmil8k.err; tail -c 300 $O/bench_line_abmil8k.json; echo
+timeout 600 python bench.py --full --mode patch --patches 32768 --pool 16 --steps 20 --no-extras > $O/bench_line_esat32k.json 2> $O/bench_line_esat32k.err
 timeout 1800 bash tools/two_rank_one_gpu.sh > $O/two_rank_default_flags.log 2>&1; tail -c 400 $O/two_rank_default_flags.log; echo

@@ -4,7 +4,7 @@ cd $GRAFT_REPO_ROOT
 STEPS=${1:-60}; ROUNDS=${2:-3}
 for r in $(seq $ROUNDS); do for form in two one; do
   echo -n "ADVMIL_ATTN_BWD=$form  "
-  ADVMIL_ATTN_BWD=$form timeout 600 python bench.py --mode patch --patches 32768 --pool 16 --steps $STEPS --no-extras --no-cpu-baseline 2>/dev/null | python3 -c "
+  ADVMIL_ATTN_BWD=$form timeout 600 python bench.py --full --mode patch --patches 32768 --pool 16 --steps $STEPS --no-extras --no-cpu-baseline 2>/dev/null | python3 -c "
 import json,sys
 for l in sys.stdin:
     l=l.strip()

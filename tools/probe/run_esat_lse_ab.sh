@@ -2,7 +2,7 @@
 cd $GRAFT_REPO_ROOT
 for r in 1 2 3; do for v in 0 1; do
   echo -n "ADVMIL_MHA_LSE_MEMO=$v  "
-  ADVMIL_MHA_LSE_MEMO=$v timeout 600 python bench.py --mode patch --patches 32768 --pool 16 --steps 60 --no-extras --no-cpu-baseline 2>/dev/null | python3 -c "
+  ADVMIL_MHA_LSE_MEMO=$v timeout 600 python bench.py --full --mode patch --patches 32768 --pool 16 --steps 60 --no-extras --no-cpu-baseline 2>/dev/null | python3 -c "
 import json,sys
 for l in sys.stdin:
     l=l.strip()

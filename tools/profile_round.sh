@@ -8,8 +8,8 @@ O=gpurun_out/prof_${ROUND:-r06}
 mkdir -p $O
 what="${1:-all}"
 if [ "$what" = all ] || [ "$what" = bench ]; then
-  timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/bench_abmil -- python3 bench.py --steps 30 --no-extras --no-cpu-baseline > $O/bench_abmil.log 2>&1
-  timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/bench_esat32k -- python3 bench.py --mode patch --patches 32768 --pool 16 --steps 10 --no-extras --no-cpu-baseline > $O/bench_esat32k.log 2>&1
+  timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/bench_abmil -- python3 bench.py --full --steps 30 --no-extras --no-cpu-baseline > $O/bench_abmil.log 2>&1
+  timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/bench_esat32k -- python3 bench.py --full --mode patch --patches 32768 --pool 16 --steps 10 --no-extras --no-cpu-baseline > $O/bench_esat32k.log 2>&1
 fi
 if [ "$what" = all ] || [ "$what" = pool ]; then
   timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/pool16 -- python3 tools/pool_bench.py 8192 16 40 > $O/pool16.log 2>&1
@@ -32,7 +32,7 @@ if [ "$what" = all ] || [ "$what" = gemm ]; then
 fi
 if [ "$what" = all ] || [ "$what" = graph ]; then
   # PatchGCN (configs[4]'s backbone) at a size one GPU steps through: the step's kernels incl. genconv_fwd128 / genconv_bwd128
-  timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/bench_patchgcn -- python3 bench.py --mode graph --patches 4096 --pool 32 --steps 20 --no-extras --no-cpu-baseline > $O/bench_patchgcn.log 2>&1
+  timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/bench_patchgcn -- python3 bench.py --full --mode graph --patches 4096 --pool 32 --steps 20 --no-extras --no-cpu-baseline > $O/bench_patchgcn.log 2>&1
 fi
 if [ "$what" = all ] || [ "$what" = genconv ]; then
   # GENConv aggregation kernels alone (configs[4]'s sparse gather) at the step's block-diagonal graph

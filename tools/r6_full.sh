@@ -2,7 +2,7 @@ cd "${GRAFT_REPO_ROOT:-.}"
 export TMPDIR=/tmp
 O=gpurun_out/r6_full
 mkdir -p $O
-timeout 1500 python bench.py "$@" > $O/line.json 2> $O/line.err
+timeout 1500 python bench.py --full "$@" > $O/line.json 2> $O/line.err
 python - <<'PY'
 import json
 d=json.loads(open("gpurun_out/r6_full/line.json").read().strip().splitlines()[-1])
