@@ -38,6 +38,18 @@ def _drop(x, masks, key):
     return x if m is None else x * m
 
 
+def _relu(z, taps=None, site=""):
+    """relu(z). `taps` (a list, or None = nothing recorded, nothing changed): each ReLU appends {'site', 'Z', 'Y'} -- its input
+    with its graph back to the parameters and its output with .grad retained, so that after backward() a test can see which
+    entries sit at the branch point and what a branch taken the other way would do (tests/boundary.py)."""
+    y = torch.relu(z)
+    if taps is not None:
+        if y.requires_grad:
+            y.retain_grad()
+        taps.append({"site": site, "Z": z, "Y": y})
+    return y
+
+
 def _sub(P, prefix):
     n = len(prefix)
     return {k[n:]: v for k, v in P.items() if k.startswith(prefix)}
@@ -57,21 +69,21 @@ def attn_net_gated(P, h, masks=None, mkey=""):
 # ---------------------------------------------------------------------------------------
 # a2 ABMIL — model/backbone.py:54-86
 # ---------------------------------------------------------------------------------------
-def abmil(P, x, masks=None):
+def abmil(P, x, masks=None, taps=None):
     """x[1,N,C] -> (H[1,dim_out], A[1,N] softmax attention). backbone.py:79-86."""
     x = x.squeeze(0)
-    h = _drop(torch.relu(_lin(P, "attention_net.0", x)), masks, "fc")
+    h = _drop(_relu(_lin(P, "attention_net.0", x), taps, "attention_net.0"), masks, "fc")
     s = attn_net_gated(_sub(P, "attention_net.3."), h, masks)          # [N,1]
     A = torch.softmax(s.t(), dim=1)                                    # [1,N]
     pooled = A @ h                                                     # [1,D]
-    H = _drop(torch.relu(_lin(P, "rho.0", pooled)), masks, "rho")
+    H = _drop(_relu(_lin(P, "rho.0", pooled), taps, "rho.0"), masks, "rho")
     return H, A
 
 
 # ---------------------------------------------------------------------------------------
 # a3 DeepAttMISL — model/backbone.py:89-123
 # ---------------------------------------------------------------------------------------
-def deep_att_misl(P, x, cluster_id, masks=None, num_clusters=8):
+def deep_att_misl(P, x, cluster_id, masks=None, num_clusters=8, taps=None):
     """phis is a 1x1 conv == FC+ReLU per patch; per-cluster mean; empty cluster -> zeros
     (backbone.py:112-116); then FC+ReLU+Dropout -> gated attention over the 8 rows -> mm."""
     x = x.squeeze(0)
@@ -84,9 +96,9 @@ def deep_att_misl(P, x, cluster_id, masks=None, num_clusters=8):
         if xc.shape[0] == 0:
             rows.append(torch.zeros(W.shape[0], dtype=x.dtype))
         else:
-            rows.append(torch.relu(xc @ W.t() + b).mean(dim=0))
+            rows.append(_relu(xc @ W.t() + b, taps, f"phis.0/{c}").mean(dim=0))
     hc = torch.stack(rows, dim=0)                                      # [8,D]
-    h = _drop(torch.relu(_lin(P, "attention_net.0", hc)), masks, "fc")
+    h = _drop(_relu(_lin(P, "attention_net.0", hc), taps, "attention_net.0"), masks, "fc")
     s = attn_net_gated(_sub(P, "attention_net.3."), h, masks)
     A = torch.softmax(s.t(), dim=1)
     return A @ h, A
@@ -107,7 +119,7 @@ def gapool(P, x, masks=None, mkey="pool_"):
 # ---------------------------------------------------------------------------------------
 # a5 AVGPoolPatchEmbedding — model/backbone_utils.py:129-168 (+ sequence2square 62-77)
 # ---------------------------------------------------------------------------------------
-def avgpool_patch_embedding(P, x):
+def avgpool_patch_embedding(P, x, taps=None, site="embedding"):
     """ksize=1, stride=1, scale=4: the 1x1 conv on 4x4 tiles is a row-wise FC; then
     LayerNorm(d, eps 1e-5) -> ReLU -> mean over each consecutive 16 rows. N % 16 == 0
     (backbone_utils.py:65)."""
@@ -116,7 +128,7 @@ def avgpool_patch_embedding(P, x):
     W = P["conv.weight"].reshape(P["conv.weight"].shape[0], -1)
     y = x @ W.t() + P["conv.bias"]
     y = F.layer_norm(y, (W.shape[0],), P["norm.weight"], P["norm.bias"], 1e-5)
-    y = torch.relu(y)
+    y = _relu(y, taps, site)
     return y.reshape(B, N // 16, 16, W.shape[0]).mean(dim=2)
 
 
@@ -124,7 +136,7 @@ def avgpool_patch_embedding(P, x):
 # a6 TransformerEncoderLayer (post-norm, relu, batch_first) — backbone_utils.py:113-127;
 # arithmetic is torch's nn.TransformerEncoderLayer / nn.MultiheadAttention (third party).
 # ---------------------------------------------------------------------------------------
-def transformer_encoder_layer(P, x, nhead=8, masks=None):
+def transformer_encoder_layer(P, x, nhead=8, masks=None, taps=None):
     """x[1,L,d]. masks: 'attn' [1,H,L,L] on the softmax probabilities, 'drop1'/'drop2' on the
     two residual branches, 'ffn' on relu(linear1)."""
     B, L, d = x.shape
@@ -139,7 +151,7 @@ def transformer_encoder_layer(P, x, nhead=8, masks=None):
     o = (p @ v).transpose(1, 2).reshape(B, L, d)
     o = _lin(P, "self_attn.out_proj", o)
     x = F.layer_norm(x + _drop(o, masks, "drop1"), (d,), P["norm1.weight"], P["norm1.bias"], 1e-5)
-    f = _drop(torch.relu(_lin(P, "linear1", x)), masks, "ffn")
+    f = _drop(_relu(_lin(P, "linear1", x), taps, "linear1"), masks, "ffn")
     f = _lin(P, "linear2", f)
     x = F.layer_norm(x + _drop(f, masks, "drop2"), (d,), P["norm2.weight"], P["norm2.bias"], 1e-5)
     return x
@@ -149,9 +161,9 @@ def transformer_encoder_layer(P, x, nhead=8, masks=None):
 # a7 DualTrans_HS (ESAT) — model/backbone.py:171-196 (coord=None: PE skipped,
 # model_handler.py:390)
 # ---------------------------------------------------------------------------------------
-def dualtrans_hs(P, x, masks=None, nhead=8):
-    emb = avgpool_patch_embedding(_sub(P, "patch_embedding_layer."), x)
-    feat = transformer_encoder_layer(_sub(P, "patch_encoder_layer.layers.0."), emb, nhead, masks)
+def dualtrans_hs(P, x, masks=None, nhead=8, taps=None):
+    emb = avgpool_patch_embedding(_sub(P, "patch_embedding_layer."), x, taps, "patch_embedding_layer")
+    feat = transformer_encoder_layer(_sub(P, "patch_encoder_layer.layers.0."), emb, nhead, masks, taps)
     H, attn = gapool(_sub(P, "pool."), feat, masks)
     return H, attn.squeeze(1)
 
@@ -192,28 +204,28 @@ def patch_gcn(P, x, edge_index, masks=None):
 # ---------------------------------------------------------------------------------------
 # a8 EmbedXLayer — model/model_utils.py:188-210; make_efficient_mlp_layer 157-166
 # ---------------------------------------------------------------------------------------
-def _eff_mlp(P, x, masks, key):
-    h = _drop(torch.relu(_lin(P, "0", x)), masks, key)
+def _eff_mlp(P, x, masks, key, taps=None):
+    h = _drop(_relu(_lin(P, "0", x), taps, key + ".0"), masks, key)
     return _lin(P, "3", h)
 
 
-def embed_x_layer(P, x, masks=None):
+def embed_x_layer(P, x, masks=None, taps=None):
     """x[1,N,C] -> (fc_bag[1,d], fc_ins[1,L,d], pool attention[1,L])."""
-    emb_ins = avgpool_patch_embedding(_sub(P, "embedding."), x)
-    fc_ins = _eff_mlp(_sub(P, "fc1."), emb_ins, masks, "fc1")
+    emb_ins = avgpool_patch_embedding(_sub(P, "embedding."), x, taps, "embedding")
+    fc_ins = _eff_mlp(_sub(P, "fc1."), emb_ins, masks, "fc1", taps)
     emb_bag, attn = gapool(_sub(P, "pool."), fc_ins, masks)
-    fc_bag = _eff_mlp(_sub(P, "fc2."), emb_bag, masks, "fc2")
+    fc_bag = _eff_mlp(_sub(P, "fc2."), emb_bag, masks, "fc2", taps)
     return fc_bag, fc_ins, attn.squeeze(1)
 
 
 # ---------------------------------------------------------------------------------------
 # a9 make_embedding_y_layer — model/model_utils.py:168-186 (norm False, dropout 0.0 in cfg)
 # ---------------------------------------------------------------------------------------
-def embed_y(P, t, masks=None):
+def embed_y(P, t, masks=None, taps=None):
     i = 0
     h = t
     while f"{i}.0.weight" in P:
-        h = _drop(torch.relu(_lin(P, f"{i}.0", h)), masks, f"y{i}")
+        h = _drop(_relu(_lin(P, f"{i}.0", h), taps, f"net_pair_two.{i}.0"), masks, f"y{i}")
         i += 1
     return h
 
@@ -221,9 +233,9 @@ def embed_y(P, t, masks=None):
 # ---------------------------------------------------------------------------------------
 # a10 PrjDiscriminator (RLIP) — model/GANSurv.py:71-105; a11 Discriminator — 52-68
 # ---------------------------------------------------------------------------------------
-def prj_discriminator(P, x, t, inner_product="instance", prj_path="x", masks=None):
-    hid_t = embed_y(_sub(P, "net_pair_two."), t, masks)                 # [1,C']
-    hid_x, fc_ins, _ = embed_x_layer(_sub(P, "net_pair_one."), x, masks)
+def prj_discriminator(P, x, t, inner_product="instance", prj_path="x", masks=None, taps=None):
+    hid_t = embed_y(_sub(P, "net_pair_two."), t, masks, taps)           # [1,C']
+    hid_x, fc_ins, _ = embed_x_layer(_sub(P, "net_pair_one."), x, masks, taps)
     if inner_product == "bag":
         out = (hid_t * hid_x).sum(dim=-1, keepdim=True)                 # GANSurv.py:92-94
     else:
@@ -234,26 +246,26 @@ def prj_discriminator(P, x, t, inner_product="instance", prj_path="x", masks=Non
     return out
 
 
-def discriminator_cat(P, x, t, masks=None):
-    hid_t = embed_y(_sub(P, "net_pair_two."), t, masks)
-    hid_x, _, _ = embed_x_layer(_sub(P, "net_pair_one."), x, masks)
+def discriminator_cat(P, x, t, masks=None, taps=None):
+    hid_t = embed_y(_sub(P, "net_pair_two."), t, masks, taps)
+    hid_x, _, _ = embed_x_layer(_sub(P, "net_pair_one."), x, masks, taps)
     return _lin(P, "fc", torch.cat([hid_x, hid_t], dim=1))
 
 
 # ---------------------------------------------------------------------------------------
 # a12 Generator — model/GANSurv.py:13-49; make_noise_mlp_layer model_utils.py:116-133
 # ---------------------------------------------------------------------------------------
-def backbone_forward(kind, P, x, x_ext, masks=None):
+def backbone_forward(kind, P, x, x_ext, masks=None, taps=None):
     if kind == "patch":
-        return dualtrans_hs(P, x, masks)
+        return dualtrans_hs(P, x, masks, taps=taps)
     if kind == "cluster":
-        return deep_att_misl(P, x, x_ext, masks)
+        return deep_att_misl(P, x, x_ext, masks, taps=taps)
     if kind == "graph":
         return patch_gcn(P, x.squeeze(0) if x.dim() == 3 else x, x_ext, masks)
-    return abmil(P, x, masks)
+    return abmil(P, x, masks, taps)
 
 
-def generator_head(P, H, noise_flags, noise=None, masks=None, out_scale="sigmoid"):
+def generator_head(P, H, noise_flags, noise=None, masks=None, out_scale="sigmoid", taps=None):
     """noise: list of tensors, one per layer whose flag is 1 (None/zeros = zero_noise)."""
     nlayers = len(noise_flags)
     it = iter(noise) if noise is not None else None
@@ -267,7 +279,7 @@ def generator_head(P, H, noise_flags, noise=None, masks=None, out_scale="sigmoid
         if i < nlayers - 1:
             if f"MLPs.{i}.1.weight" in P:                               # gen_norm=True variant
                 h = F.layer_norm(h, (h.shape[-1],), P[f"MLPs.{i}.1.weight"], P[f"MLPs.{i}.1.bias"], 1e-5)
-            h = _drop(torch.relu(h), masks, f"mlp{i}")
+            h = _drop(_relu(h, taps, f"MLPs.{i}"), masks, f"mlp{i}")
         H = h
     if out_scale == "sigmoid":
         return torch.sigmoid(H)
@@ -277,9 +289,9 @@ def generator_head(P, H, noise_flags, noise=None, masks=None, out_scale="sigmoid
 
 
 def generator(P, x, x_ext, kind="abmil", noise_flags=(0, 1), noise=None, masks=None,
-              out_scale="sigmoid", return_attn=False):
-    H, A = backbone_forward(kind, _sub(P, "backbone."), x, x_ext, masks)
-    y = generator_head(P, H, list(noise_flags), noise, masks, out_scale)
+              out_scale="sigmoid", return_attn=False, taps=None):
+    H, A = backbone_forward(kind, _sub(P, "backbone."), x, x_ext, masks, taps)
+    y = generator_head(P, H, list(noise_flags), noise, masks, out_scale, taps)
     return (y, A, H) if return_attn else y
 
 
@@ -375,10 +387,17 @@ class StepConfig:
         del self.__dict__["self"]
 
 
-def _netD(cfg, PD, x, t, masks):
+def _netD(cfg, PD, x, t, masks, taps=None):
     if cfg.disc_type == "prj":
-        return prj_discriminator(PD, x, t, cfg.inner_product, cfg.prj_path, masks)
-    return discriminator_cat(PD, x, t, masks)
+        return prj_discriminator(PD, x, t, cfg.inner_product, cfg.prj_path, masks, taps)
+    return discriminator_cat(PD, x, t, masks, taps)
+
+
+def _bag_taps(taps, i, which):
+    """The tap list of bag i's `which` forward ('real' / 'fake' / 'gen'), registered in the caller's dict; None when not asked for."""
+    if taps is None:
+        return None
+    return taps.setdefault((i, which), [])
 
 
 def _req(P):
@@ -386,21 +405,23 @@ def _req(P):
 
 
 def update_disc(cfg, PG, PD, bags, noise_d, masks_real=None, masks_fake=None,
-                n_real_global=None, n_fake_global=None, visible=None):
+                n_real_global=None, n_fake_global=None, visible=None, taps=None):
     """netD.train(), netG.eval() (model_handler.py:355-356). bags = [(x[1,N,C], x_ext, y[1,2])].
     noise_d[i] = generator noise tensors for bag i. masks_real/fake[i] = D dropout masks for the
     real / fake forward of bag i. Returns (losses dict, grads of D, preds, f_fake list).
-    n_*_global: denominators when the bags are one rank's shard of a larger step batch."""
+    n_*_global: denominators when the bags are one rank's shard of a larger step batch.
+    taps: a dict to fill with {(bag index, 'real' | 'fake'): [ReLU taps of that forward]} (`_relu`); the graph is then kept and the
+    returned dict of gradients also holds the parameters themselves under '__params__' (for vector-Jacobian products of a tap)."""
     PDg = _req(PD)
     reals, fakes, preds = [], [], []
     for i, (x, x_ext, y) in enumerate(bags):
         t, e = y[:, [0]], y[:, [1]]
         if e.item() == 1 and (visible is None or visible[i]):           # 373-379: event bag with a visible label
-            reals.append(_netD(cfg, PDg, x, t, None if masks_real is None else masks_real[i]).reshape(-1))
+            reals.append(_netD(cfg, PDg, x, t, None if masks_real is None else masks_real[i], _bag_taps(taps, i, "real")).reshape(-1))
         with torch.no_grad():                                           # detached at 400
             pred = generator(PG, x, x_ext, cfg.kind, cfg.noise_flags, noise_d[i], None, cfg.out_scale)
         preds.append(pred)
-        fakes.append(_netD(cfg, PDg, x, pred, None if masks_fake is None else masks_fake[i]).reshape(-1))
+        fakes.append(_netD(cfg, PDg, x, pred, None if masks_fake is None else masks_fake[i], _bag_taps(taps, i, "fake")).reshape(-1))
     real = torch.cat(reals) if reals else None
     fake = torch.cat(fakes)
     if n_fake_global is None:
@@ -409,21 +430,25 @@ def update_disc(cfg, PG, PD, bags, noise_d, masks_real=None, masks_fake=None,
         loss = -(1.0 - torch.log(torch.sigmoid(fake) + 1e-8)).sum() / n_fake_global
         if real is not None:
             loss = loss - torch.log(torch.sigmoid(real) + 1e-8).sum() / n_real_global
-    loss.backward()
+    if taps is None:
+        loss.backward()
+    else:
+        loss.backward(retain_graph=True)
+        taps["__params__"] = PDg
     grads = {k: v.grad for k, v in PDg.items() if v.grad is not None}
     logs = {"Loss_D": loss.item(), "D_real": 0.0 if real is None else real.mean().item(),
             "D_fake": fake.mean().item()}
     return logs, grads, preds, [f.detach() for f in fakes]
 
 
-def update_gen(cfg, PG, PD, bags, noise_g, masks_g=None, n_global=None, visible=None):
+def update_gen(cfg, PG, PD, bags, noise_g, masks_g=None, n_global=None, visible=None, taps=None):
     """netD.eval(), netG.train() (model_handler.py:432-433). visible[i] False = label invisible ('wolabel' mode): the bag
-    still feeds the adversarial term but not the supervised loss (473-480)."""
+    still feeds the adversarial term but not the supervised loss (473-480). taps: as in update_disc, keys (bag index, 'gen')."""
     PGg = _req(PG)
     preds, fakes = [], []
     for i, (x, x_ext, y) in enumerate(bags):
         pred = generator(PGg, x, x_ext, cfg.kind, cfg.noise_flags, noise_g[i],
-                         None if masks_g is None else masks_g[i], cfg.out_scale)
+                         None if masks_g is None else masks_g[i], cfg.out_scale, taps=_bag_taps(taps, i, "gen"))
         preds.append(pred)
         fakes.append(_netD(cfg, PD, x, pred, None).reshape(-1))
     fake = torch.cat(fakes)
@@ -440,11 +465,13 @@ def update_gen(cfg, PG, PD, bags, noise_g, masks_g=None, n_global=None, visible=
         t_reg = recon_loss(P_, T_, E_, cfg.recon_alpha, cfg.recon_gamma, cfg.recon_norm) * (len(bags) / n_global)
     total = t_reg + cfg.gan_coef * gen_loss if cfg.gan_coef != 0.0 else t_reg  # 481-484
     l1 = loss_reg_l1(cfg.l1_coef, PGg.values())                         # 485
+    if taps is not None:
+        taps["__params__"] = PGg
     if n_global is None:
         total = total + l1
-        total.backward()
+        total.backward(retain_graph=taps is not None)
     else:  # L1 gradient is added once after the all-reduce; keep it out of the shard's backward
-        total.backward()
+        total.backward(retain_graph=taps is not None)
         total = total + l1
     grads = {k: v.grad for k, v in PGg.items() if v.grad is not None}
     logs = {"Loss_G_fake": gen_loss.item(), "Loss_G_time": t_reg.item(),

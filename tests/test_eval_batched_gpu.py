@@ -10,6 +10,43 @@ from tests import helpers as H
 from tests.test_parity_gpu import DEV, build_disc, build_generator, load_synth
 
 pytestmark = pytest.mark.gpu
+TOL = 2e-5
+
+
+class bf16x3_mode:
+    """The arithmetic the evaluation ships in (the suite's default is `exact`, tests/conftest.py); put back on exit."""
+
+    def __enter__(self):
+        from advmil_amd import ops
+        self.prev = ops.get_gemm_mode()
+        ops.set_gemm_mode("bf16x3")
+
+    def __exit__(self, *exc):
+        from advmil_amd import ops
+        ops.set_gemm_mode(self.prev)
+        return False
+
+
+def vs_float64_oracle(res, kind, disc, g, d, items, noises=None, rows=None):
+    """The batched result against oracle.test_model_bag in float64 on the same bags and noise, at TOL = 2e-5."""
+    from oracle import advmil_oracle as O
+    cfg = O.StepConfig(kind=kind, disc_type=disc[0], inner_product=disc[1], prj_path=disc[2])
+    PG = {k: v.detach().cpu().double() for k, v in g.state_dict().items()}
+    PD = {k: v.detach().cpu().double() for k, v in d.state_dict().items()}
+    worst = {}
+    for r, i in enumerate(range(len(items)) if rows is None else rows):
+        x = items[i][1][0].cpu().double()
+        ext = items[i][1][1].cpu() if kind == "cluster" else None
+        nz = None if noises is None else [n.cpu().double() for n in noises[i]]
+        y_hat, f_fake, dist, avg = O.test_model_bag(cfg, PG, PD, x, ext, None if nz is None else nz[:1], [] if nz is None else [[n] for n in nz[1:]])
+        want = {"y_hat": y_hat, "f_fake": f_fake}
+        if "dist_y_hat" in res:
+            want["dist_y_hat"], want["avg_y_hat"] = dist, avg
+        for k, w in want.items():
+            dv = float((res[k][r].double().reshape(-1) - w.reshape(-1)).abs().max())
+            worst[k] = max(worst.get(k, 0.0), dv)
+            assert dv <= TOL, (k, i, dv)
+    print("[eval bf16x3 vs float64]", {k: f"{v:.2e}" for k, v in worst.items()})
 
 
 class Dataset:
@@ -53,6 +90,17 @@ def same(a, b, tol=2e-6):
 def test_batched_eval_equals_per_bag_eval(kind, disc):
     """Ragged bags, injected head noise (so both paths see the same draws), 7 samples per bag; batches of 3 with a remainder; one
     bag that is already a device tensor drops to the per-bag path in the middle of the epoch (order and results unchanged)."""
+    batched_vs_per_bag(kind, disc)
+
+
+@pytest.mark.parametrize("kind,disc", [("abmil", ("prj", "instance", "x")), ("patch", ("prj", "bag", "x")), ("cluster", ("cat", "bag", None))])
+def test_bf16x3_batched_eval_equals_per_bag_eval(kind, disc):
+    """... in bf16x3, and the batched result against the float64 oracle as well."""
+    with bf16x3_mode():
+        batched_vs_per_bag(kind, disc, oracle=True)
+
+
+def batched_vs_per_bag(kind, disc, oracle=False):
     from advmil_amd.model import MyHandler
     g, d = nets(kind, disc)
     lens = (256, 128, 512, 64, 192, 384, 320)
@@ -66,11 +114,40 @@ def test_batched_eval_equals_per_bag_eval(kind, disc):
     one = MyHandler.test_model(g, d, kind, items, times_test_sample=1, noise=[nz[:1] for nz in noises])
     assert set(one) == {"idx", "y", "y_hat", "f_fake"}
     same({k: one[k] for k in ("y_hat", "f_fake")}, {k: per_bag[k] for k in ("y_hat", "f_fake")})
+    if oracle:
+        vs_float64_oracle(batched, kind, disc, g, d, items, noises)
 
 
 def test_eval_bags_stay_in_hbm_between_epochs():
     """Second evaluation pass over the same dataset (another loader object, another order): no host bag is read -- the host tensors
     are poisoned in between -- and the predictions are those of the first pass, re-ordered. Slabs large enough for operand planes."""
+    eval_bags_stay_in_hbm()
+
+
+def test_bf16x3_eval_bags_stay_in_hbm_between_epochs():
+    """... in bf16x3, where every slab large enough for operand planes (ops.slab_takes_planes) must reach the kernels WITH them -- split
+    by the staging slab in the first pass, gathered from the cached bags' planes in the second (asserted) -- and against the float64
+    oracle as well."""
+    from advmil_amd import ops
+    from advmil_amd.model import MyHandler
+    slabs = []
+    real = MyHandler._slab_build_static
+
+    def spy(xs, resident_planes=True, pad=0):
+        X = real(xs, resident_planes, pad)
+        slabs.append((int(X.shape[0]), getattr(X, "_advmil_planes", None) is not None, bool(ops.slab_takes_planes(X.shape[0], X.shape[1]))))
+        return X
+    MyHandler._slab_build_static = staticmethod(spy)
+    try:
+        with bf16x3_mode():
+            eval_bags_stay_in_hbm(oracle=True)
+    finally:
+        MyHandler._slab_build_static = staticmethod(real)
+    print("[eval bf16x3] slabs (rows, carries planes, large enough for planes):", slabs)
+    assert sum(1 for _, _, big in slabs if big) >= 4 and all(has for _, has, big in slabs if big), slabs
+
+
+def eval_bags_stay_in_hbm(oracle=False):
     from advmil_amd import ingest
     from advmil_amd.model import MyHandler
     g, d = nets("abmil")
@@ -82,6 +159,8 @@ def test_eval_bags_stay_in_hbm_between_epochs():
     a = MyHandler.test_model(g, d, "abmil", Loader(ds), noise=noises, batch_bags=2)
     assert cache.misses - m0 == len(lens) and cache.hits == h0
     torch.cuda.synchronize()
+    if oracle:
+        vs_float64_oracle(a, "abmil", ("prj", "instance", "x"), g, d, ds.items, noises)
     for it in ds.items:
         it[1][0].copy_(H.poison_host_bag(it[1][0]))
     order = [3, 0, 4, 1, 2]
@@ -160,6 +239,25 @@ def test_degenerate_loaders():
     same(a, b)
     cl = h._train_each_epoch(five, "train")                                    # one step of 4 bags, the fifth is dropped
     assert cl["y_hat"].shape == (4, 1) and len(h.pop_logs()) == 2 and bool(torch.isfinite(cl["f_fake"]).all())
+
+
+def test_bf16x3_padded_eval_slab():
+    """The padded case of test_degenerate_loaders (slabs of 4 + 1 bags, the last one 4112 rows + pad) in bf16x3: batched == per bag, and
+    the batched result against the float64 oracle."""
+    from advmil_amd.config import default_cfg
+    from advmil_amd.model import MyHandler
+    from advmil_amd import ops
+    prev = ops.get_gemm_mode()
+    try:
+        h = MyHandler(default_cfg(bcb_mode="abmil", bp_every_batch=4, gemm_mode="bf16x3"), device=DEV)
+        load_synth(h.netG, "G-abmil:"); load_synth(h.netD, "D-prj:")
+        five = make("abmil", (64, 16, 128, 16, 4112))
+        a = MyHandler.test_model(h.netG, h.netD, "abmil", five, test_zero_noise=True, batch_bags=4)
+        b = MyHandler.test_model(h.netG, h.netD, "abmil", five, test_zero_noise=True, batch_bags=1)
+        same(a, b)
+        vs_float64_oracle(a, "abmil", ("prj", "instance", "x"), h.netG, h.netD, five)
+    finally:
+        ops.set_gemm_mode(prev)
 
 
 def test_a_cache_hit_is_checked_against_the_bag_the_loader_hands_over():

@@ -178,39 +178,31 @@ def gradients_before_adam(which, kind, lens, events, visible, bag_seed0=40, **cf
         return {k_: v_.double() for k_, v_ in d.items()}
     bags64 = [(x_.double(), None if e_ is None else e_.double(), y_.double()) for x_, e_, y_ in bags]
     nd64, ng64 = [[n[0].double()] for n in nd], [[n[0].double()] for n in ng]
-    _, gD, _, _ = O.update_disc(cfg, dbl(PG), dbl(PD), bags64, nd64, visible=vis)
-    _, gG, _ = O.update_gen(cfg, dbl(PG), dbl(PD), bags64, ng64, visible=vis)
-    # Units of a region embedding (FC -> LayerNorm -> ReLU) that hold a LayerNorm output within fp32 round-off of 0 in float64: which ReLU
-    # branch such an entry takes in ANY fp32 evaluation is decided by the summation order (a step of 4 000 patches holds 0.5-2 M such outputs:
-    # about every second case has one below 3e-7), and the unit's own weight / bias / gamma / beta gradients move by the row's whole
-    # contribution when it flips. They are a property of the input, not of a kernel -> not compared; every other
-    # entry is.
-    Xall = torch.cat([b_[0].reshape(-1, b_[0].shape[-1]) for b_ in bags64])
-    skip = {}
-    for P_, pre, on in ((PD, "net_pair_one.embedding.", True), (PG, "backbone.patch_embedding_layer.", kind == "patch")):
-        if not on or pre + "conv.weight" not in P_:
-            continue
-        Wd = P_[pre + "conv.weight"].double().reshape(P_[pre + "conv.weight"].shape[0], -1)
-        ln = torch.nn.functional.layer_norm(Xall @ Wd.t() + P_[pre + "conv.bias"].double(), (Wd.shape[0],), P_[pre + "norm.weight"].double(),
-                                            P_[pre + "norm.bias"].double(), 1e-5)
-        units = sorted(set((ln.abs() < 1.5e-6).nonzero()[:, 1].tolist()))
-        for suffix in ("conv.weight", "conv.bias", "norm.weight", "norm.bias"):
-            skip[pre + suffix] = units
-    for net, want in ((h.netD, gD), (h.netG, gG)):
+    tD, tG = {}, {}
+    _, gD, _, _ = O.update_disc(cfg, dbl(PG), dbl(PD), bags64, nd64, visible=vis, taps=tD)
+    _, gG, _ = O.update_gen(cfg, dbl(PG), dbl(PD), bags64, ng64, visible=vis, taps=tG)
+    # Entries of a first layer / region embedding (FC -> LayerNorm -> ReLU) whose pre-activation is within fp32 round-off of 0 in float64:
+    # which ReLU branch such an entry takes in ANY fp32 evaluation is decided by the summation order (a step of 4 000 patches holds 0.5-2 M
+    # such outputs: about every second case has one below 3e-7), and the unit's own weight / bias / gamma / beta gradients move by the
+    # row's whole contribution when it flips. The ReLU-boundary rule (tests/boundary.py) accounts for exactly those
+    # flips -- the reference names the undecided entries and the one direction each can move the gradients in -- and every entry of every
+    # parameter is compared, the units that hold such an entry included.
+    from advmil_amd import ops
+    from tests import boundary as B
+    _, bD, _, bG = B.step_sites(kind, tD, tG, bags, PG, PD, deep=False)
+    mode_ = ops.get_gemm_mode()
+    for tag, net, want, site in (("D", h.netD, gD, bD), ("G", h.netG, gG, bG)):
+        got = {}
         for k, p in net.named_parameters():
-            w = want.get(k)
-            got = torch.zeros_like(p) if p.grad is None else p.grad
-            if w is None:
-                assert float(got.abs().max()) == 0.0, k
+            g_ = torch.zeros_like(p) if p.grad is None else p.grad
+            if k not in want:
+                assert float(g_.abs().max()) == 0.0, k
                 continue
-            if skip.get(k):
-                keep = torch.ones(w.shape[0], dtype=torch.bool)
-                keep[skip[k]] = False
-                w, got = w[keep], got[keep.to(got.device)]
-            scale = float(w.abs().max())
-            # (+ 2.5e-7: gradients that are exactly 0 in exact arithmetic -- the logit's additive bias under hinge / wasserstein, 1 - 1 --
-            # come out as fp32 round-off of the cancelling terms here and as 1e-16 in float64)
-            assert float((got.cpu().double() - w).abs().max()) <= 2e-5 * scale + 2.5e-7, (which, kind, k, float((got.cpu().double() - w).abs().max()), scale)
+            got[k] = g_
+        # (+ 2.5e-7: gradients that are exactly 0 in exact arithmetic -- the logit's additive bias under hinge / wasserstein, 1 - 1 --
+        # come out as fp32 round-off of the cancelling terms here and as 1e-16 in float64)
+        sites = [] if site is None else [B.bag_fed_site(*site, mode_)]
+        B.assert_grads_match_up_to_relu_branches(got, want, sites, 2e-5, 2.5e-7, label=f"{which} {kind} {lens} {tag}")
 
 
 @pytest.mark.parametrize("over", [dict(disc_type="cat", disc_prj_path=None), dict(disc_prj_iprd="bag"), dict(disc_prj_path="y"),

@@ -230,22 +230,27 @@ def test_train_mode_dropout_parity_vs_oracle(kind):
     mkd = lambda e: H.T(synth.dropout_keep(2024, e[1], int(np.prod(e[2])), e[3]).reshape(e[2]).astype(np.float32) / (1 - e[3]))
     md = {"fc1": mask("dx_fc1").reshape(1, L, 64), "pool_a": mkd(gd[0]).reshape(1, L, 128), "pool_b": mkd(gd[1]).reshape(1, L, 128),
           "fc2": small("dx_fc2.2", 0.25).reshape(1, 64)}
-    PGr = {k: v.clone().requires_grad_(True) for k, v in PG.items()}
-    PDr = {k: v.clone().requires_grad_(True) for k, v in PD.items()}
+    # the oracle in FLOAT64: the ReLU-boundary rule (tests/boundary.py) takes its undecided entries from it
+    from tests import boundary as B
+    PGr = {k: v.double().requires_grad_(True) for k, v in PG.items()}
+    PDr = {k: v.double().requires_grad_(True) for k, v in PD.items()}
     xc = x.float().cpu()          # (a bf16 bag of the x_storage fixture: the oracle sees the same rounded values)
-    pr = O.generator(PGr, xc, None if ext is None else ext.cpu(), kind, (0, 1), [nz[0].cpu()], mg, "sigmoid")
-    fr = O.prj_discriminator(PDr, xc, pr, "instance", "x", md)
+    extc = None if ext is None else ext.cpu()
+    tg, td = [], []
+    dbl = lambda m: {k_: v_.double() for k_, v_ in m.items()}
+    pr = O.generator(PGr, xc.double(), extc, kind, (0, 1), [nz[0].cpu().double()], dbl(mg), "sigmoid", taps=tg)
+    fr = O.prj_discriminator(PDr, xc.double(), pr, "instance", "x", dbl(md), taps=td)
     (fr.sum() + 3.0 * (pr - 0.4).abs().sum()).backward()
     close(pred, pr); close(f, fr)
-    for net, Pr in ((g, PGr), (d, PDr)):
-        for k, p in net.named_parameters():
-            want = Pr[k].grad
-            if want is None:
-                continue
-            scale = float(want.abs().max()) + 1e-12
-            # (absolute floor: parameters whose true gradient is 0 -- the pooling scorer's output bias under the softmax -- hold
-            # only round-off, ~1e-7 on both sides)
-            assert float((p.grad.cpu() - want).abs().max()) <= 2e-4 * scale + 5e-7, (kind, k, float((p.grad.cpu() - want).abs().max()), scale)
+    mode = ops.get_gemm_mode()
+    sites = {"G": B.bag_fed_site(*B.generator_first_layer(kind, [tg], [(xc, extc, None)], xc[0], PG), mode),
+             "D": B.bag_fed_site(*B.disc_embedding([[td]], xc[0], PD), mode)}
+    for tag, net, Pr in (("G", g, PGr), ("D", d, PDr)):
+        want = {k: v.grad for k, v in Pr.items() if v.grad is not None}
+        got = {k: p.grad for k, p in net.named_parameters() if k in want}
+        # (absolute floor: parameters whose true gradient is 0 -- the pooling scorer's output bias under the softmax -- hold only
+        # round-off, ~1e-7: their scale is ~0 and the bound is the floor)
+        B.assert_grads_match_up_to_relu_branches(got, want, [sites[tag]], 2e-4, 5e-7, label=f"dropout parity {kind} {mode} {tag}")
 
 
 def test_config1_smoke_32_bags_of_512_default_dropout():
@@ -432,11 +437,15 @@ def test_slab_features_equal_per_bag_features(kind):
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("mode", ["exact", "bf16x3"])
 @pytest.mark.parametrize("d", [128, 256, 512])
-def test_esat_other_backbone_widths_vs_oracle(d):
+def test_esat_other_backbone_widths_vs_oracle(d, mode):
     """load_backbone('patch', [1024, d, d]) for the other widths the reference accepts (nn.TransformerEncoderLayer(d_model = d,
     nhead = 8): head_dim 16 / 32 / 64, model/backbone.py:30-33, backbone_utils.py:113-127): generator forward + every parameter
-    gradient against the oracle, dropout off, two ragged bags through the slab path."""
+    gradient against the oracle, dropout off, two ragged bags through the slab path. Both arithmetic modes: at d = 256 one unit of
+    this bag's region embedding has a LayerNorm output on the ReLU boundary and bf16x3 lands it on the other side (3 % of ONE row of the
+    first layer's weight gradient); the ReLU-boundary rule (tests/boundary.py) accounts for exactly that and for
+    nothing else. In `exact` the rule must have nothing to do: 0 branches taken."""
     from types import SimpleNamespace
     from advmil_amd import ops
     from advmil_amd.model import Generator, load_backbone
@@ -447,11 +456,8 @@ def test_esat_other_backbone_widths_vs_oracle(d):
     g.train()
     x = H.bag(31, 1024, DEV)[:, :784].contiguous()                      # 49 regions: a ragged last key tile
     nz = [H.noise_tensor("esatw", d, d // 2, DEV)]
-    # exact arithmetic, whatever an earlier file left behind: at d = 256 one unit of this bag's region embedding has a LayerNorm output on the
-    # ReLU boundary, and bf16x3 lands it on the other side (a 3 % deviation in ONE row of the first layer's weight gradient:
-    # tools/probe/widths256_rows.py, profiles/r06_fuzz_found_cases.txt; DESIGN section 2 "ReLU-boundary inputs")
     mode0 = ops.get_gemm_mode()
-    ops.set_gemm_mode("exact")
+    ops.set_gemm_mode(mode)
     try:
         pred = g(x, None, noise=nz)
         pred.sum().backward()
@@ -460,16 +466,22 @@ def test_esat_other_backbone_widths_vs_oracle(d):
     # The oracle in FLOAT64: the attention pool's fc2.bias gradient is exactly 0 (a softmax does not see a shift of its logits), and in fp32
     # the oracle returns its round-off instead -- up to 8e-9, moving with the host's thread count -- which alone fills the 1e-8 floor.
     Pr = {k: v.clone().double().requires_grad_(True) for k, v in PG.items()}
-    pr = O.generator(Pr, x.cpu().double(), None, "patch", (0, 1), [nz[0].cpu().double()], None, "sigmoid")
-    pr.sum().backward()
+    from tests import boundary as B
+    taps = []
+    pr = O.generator(Pr, x.cpu().double(), None, "patch", (0, 1), [nz[0].cpu().double()], None, "sigmoid", taps=taps)
+    pr.sum().backward(retain_graph=True)
     close(pred, pr)
+    want, got = {}, {}
     for k, p in g.named_parameters():
-        want = Pr[k].grad
-        if want is None:
+        if Pr[k].grad is None:
             assert p.grad is None or float(p.grad.abs().max()) == 0.0, k
             continue
-        scale = float(want.abs().max()) + 1e-12
-        assert float((p.grad.cpu().double() - want).abs().max()) <= 1e-4 * scale + 1e-8, (k, float((p.grad.cpu().double() - want).abs().max()), scale)
+        want[k], got[k] = Pr[k].grad, p.grad
+    xc = x.cpu()
+    sites = [B.deep_site("G MLPs.0", [[B._tap(taps, "MLPs.0")]], Pr, "MLPs.0.0.weight"),
+             B.deep_site("G linear1", [[B._tap(taps, "linear1")]], Pr, "backbone.patch_encoder_layer.layers.0.linear1.weight"),
+             B.bag_fed_site(*B.generator_first_layer("patch", [taps], [(xc, None, None)], xc[0], PG), mode)]
+    B.assert_grads_match_up_to_relu_branches(got, want, sites, 1e-4, 1e-8, label=f"ESAT d={d} {mode}", expect_no_branches=(mode == "exact"))
 
 
 def test_G1_patch_32768_eval_forward_vs_reference(golden2):
@@ -609,11 +621,6 @@ def bf16x(monkeypatch, request):
     bag0 = H.bag
 
     def bag(seed, n, device="cpu"):                          # device bags handed to a module directly: the bf16 image itself
-        if str(device) != "cpu" and seed == 5:
-            # (the dropout-parity test's bag: the bf16 image of bag 5 puts two first-layer pre-activations within 1.1e-6 of the ReLU
-            # boundary, where the fp32 kernels and the float64 arithmetic behind the oracle's autograd take different branches and
-            # dW1 moves by 2-4 % -- the boundary effect of DESIGN.md section 2, found with tools in this round; bag 1005 has none)
-            seed = 1005
         x = bag0(seed, n, device)
         return x.to(torch.bfloat16) if str(device) != "cpu" else x
     monkeypatch.setattr(H, "bag", bag)
