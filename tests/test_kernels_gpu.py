@@ -7,6 +7,7 @@ import torch
 
 from advmil_amd import synth
 from tests import helpers as H
+from tests.poison import PATTERNS, poisoned_allocations
 
 pytestmark = pytest.mark.gpu
 
@@ -275,14 +276,18 @@ def test_gemm_tn_planes_kernel_bit_identical_to_generic(ops, M, N, K):
         A = torch.randn(K, M, device="cuda", generator=g)
         B = torch.randn(K, N, device="cuda", generator=g)
         pa, pb = ops.split_planes(A), ops.split_planes(B)
-        ref = ops.gemm(A, B, False, False, M, N, K, tile=22, splits=sp, a_planes=pa, b_planes=pb)
-        got = ops.gemm(None, B, False, False, M, N, K, a_planes=pa, b_planes=pb, tile=tile, splits=sp)     # (A as planes only)
+        with poisoned_allocations(PATTERNS[0]):      # (fresh output and split-K workspace blocks hold NaN / 3.39e38, not an earlier result)
+            ref = ops.gemm(A, B, False, False, M, N, K, tile=22, splits=sp, a_planes=pa, b_planes=pb)
+        with poisoned_allocations(PATTERNS[1]):
+            got = ops.gemm(None, B, False, False, M, N, K, a_planes=pa, b_planes=pb, tile=tile, splits=sp)     # (A as planes only)
         assert torch.equal(got, ref)
         base = torch.randn(M, N, device="cuda", generator=g)
         acc_ref, acc_got = base.clone(), base.clone()
-        ops.gemm(A, B, False, False, M, N, K, out=acc_ref, ldc=N, accumulate=True, tile=22, splits=sp, a_planes=pa, b_planes=pb)
-        ops.gemm(None, B, False, False, M, N, K, out=acc_got, ldc=N, accumulate=True, a_planes=pa, b_planes=pb,
-                 **({} if planned else dict(tile=tile, splits=sp)))                    # (planned shapes: the plan picks the kernel itself)
+        with poisoned_allocations(PATTERNS[0]):
+            ops.gemm(A, B, False, False, M, N, K, out=acc_ref, ldc=N, accumulate=True, tile=22, splits=sp, a_planes=pa, b_planes=pb)
+        with poisoned_allocations(PATTERNS[1]):
+            ops.gemm(None, B, False, False, M, N, K, out=acc_got, ldc=N, accumulate=True, a_planes=pa, b_planes=pb,
+                     **({} if planned else dict(tile=tile, splits=sp)))                # (planned shapes: the plan picks the kernel itself)
         assert torch.equal(acc_got, acc_ref)
         want = (A.double().t() @ B.double())
         assert float((got.double() - want).abs().max()) <= 2e-5 * float(want.abs().max())        # (bf16x3: ~2^-17 per product)
@@ -690,13 +695,14 @@ def test_stage_bag_copies_rows_and_derives_or_copies_planes():
     assert L.advmil_stage_bag(slab2.data_ptr(), x.data_ptr(), nb, pl2.hi.data_ptr(), want.hi.data_ptr(), pl2.lo.data_ptr(), None, nb // 2, st) == EINVAL
 
 
-def test_genconv_on_random_graph_and_without_edges():
-    """The GENConv aggregation on a graph that is not a k-NN grid (random in-degrees, a hub, an isolated node, self loops) against
+def test_genconv_on_random_graph_and_without_edges(C=128):
+    """(C: the width -- 128 takes the float4 kernels, any other the generic ones; tests/test_poison_kernels_gpu.py calls this with both.)
+    The GENConv aggregation on a graph that is not a k-NN grid (random in-degrees, a hub, an isolated node, self loops) against
     float64 -- the kernels only see CSR arrays --, and a graph without edges: out = x, identity gradient (the kernels take no empty
     edge arrays; tools/probe/graph_fuzz.py)."""
     from advmil_amd import ops
     g = torch.Generator().manual_seed(3)
-    N, C, E = 300, 128, 2400
+    N, E = 300, 2400
     src = torch.randint(0, N, (E,), generator=g); dst = torch.randint(1, N, (E,), generator=g)      # node 0 receives nothing
     dst[:600] = 7                                                                                      # a hub
     src[600:640] = dst[600:640]                                                                        # self loops
