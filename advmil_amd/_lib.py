@@ -186,6 +186,18 @@ SIGNATURES = {
     "advmil_flush_sums": (c_int, [c_void_p]),
     "advmil_pending_sums": (c_int, [c_void_p]),
     "advmil_cindex_counts": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_float, c_void_p, c_void_p]),
+    "advmil_surv_metrics_cont_workspace_bytes": (c_size_t, [c_int64]),
+    "advmil_surv_metrics_cont": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_float, c_float, c_int, c_float, c_int, c_void_p,
+                                         c_void_p, c_size_t, c_void_p]),
+    "advmil_surv_metrics_disc_workspace_bytes": (c_size_t, [c_int64]),
+    "advmil_surv_metrics_disc": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_float, c_float, c_int, c_void_p,
+                                         c_void_p, c_void_p, c_size_t, c_void_p]),
+    "advmil_ple_loss_workspace_bytes": (c_size_t, [c_int64]),
+    "advmil_ple_loss": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "advmil_rank_loss_workspace_bytes": (c_size_t, [c_int64]),
+    "advmil_rank_loss_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_float, c_int, c_int, c_void_p, c_void_p, c_void_p, c_size_t,
+                                     c_void_p]),
+    "advmil_rank_loss_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_float, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
 }
 
 _lib = None

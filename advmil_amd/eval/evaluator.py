@@ -1,0 +1,257 @@
+"""eval/evaluator.py of the reference (ContSurv_Evaluator 11-130, DiscSurv_Evaluator 133-210, CoxSurv_Evaluator 213-259) with the same
+names, `kws`, `valid_metrics`, `compute(data, metrics) -> dict[str, float]` and failure behaviour. The reference answers every metric
+with its own small host computation ending in `.item()`; here one fused launch per family (advmil_surv_metrics_cont / _disc,
+advmil_ple_loss, advmil_rank_loss_fwd: csrc/survk.hip) leaves every sum in ONE device array, which is copied to the host once.
+
+`data` is the collector of `test_model`: `y` [n, 2] (time | event), `y_hat`, optional `avg_y_hat` (preferred when present, as in the
+reference), optional `f_fake`; on the host or on the device (host tensors are moved once).
+
+How a `kws` callable is dispatched: `advmil_amd.loss.utils.recon_loss` / `rank_loss` / `real_fake_loss` (bare or as a
+`functools.partial` with keyword arguments) and instances of this package's `SurvMLE` / `SurvPLE` are recognised, their parameters read
+and their arithmetic taken from the fused launch; any other callable is called on the device tensors and `.item()`-ed, as the
+reference does. There is no CPU fallback."""
+import ctypes
+import functools
+
+import torch
+
+from .. import _lib
+from ..loss import utils as LU
+from .cindex import concordance_index, concordance_index_censored
+
+_WHICH = {"bce": 0, "hinge": 1, "wasserstein": 2}
+# slots of the result array (doubles): [0, 16) the family's fused sums, [16, 20) rank_loss state, [20, 22) SurvPLE
+_RANK, _PLE, _NRES = 16, 20, 24
+
+
+class MissingFakeScores(TypeError, AttributeError):
+    """A metric over `f_fake` was asked of a collector without one (the reference fails on `None` there: TypeError from torch.mean,
+    AttributeError from `None.squeeze()`; this is both)."""
+
+
+def _device_of(data):
+    if not torch.cuda.is_available():
+        raise RuntimeError("advmil_amd.eval needs an MI355X: no ROCm device visible (no CPU fallback)")
+    y = data["y"]
+    return y.device if (torch.is_tensor(y) and y.is_cuda) else torch.device("cuda", torch.cuda.current_device())
+
+
+def _f32(x, dev):
+    return torch.as_tensor(x).to(device=dev, dtype=torch.float32).contiguous()
+
+
+def _p(t):
+    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
+
+
+def _stream(dev):
+    return ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+
+
+def _ws(nbytes, dev):
+    return torch.empty((int(nbytes) + 7) // 8, dtype=torch.float64, device=dev)
+
+
+def _recognise(fn, target, allowed):
+    """-> the keyword arguments bound to `target` (this package's function), or None when `fn` is something else."""
+    if fn is target:
+        return {}
+    if isinstance(fn, functools.partial) and fn.func is target and not fn.args and set(fn.keywords) <= set(allowed):
+        return dict(fn.keywords)
+    return None
+
+
+def _given(kws, name):
+    return kws.get(name) is not None
+
+
+def _disc_which(kws):
+    """(which code | None, generic callable | None) of kws['disc_loss']."""
+    if not _given(kws, "disc_loss"):
+        return None, None
+    k = _recognise(kws["disc_loss"], LU.real_fake_loss, ("which",))
+    if k is not None and k.get("which", "bce") in _WHICH:
+        return _WHICH[k.get("which", "bce")], None
+    return None, kws["disc_loss"]
+
+
+def _fake_of(data, dev):
+    return _f32(data["f_fake"], dev).reshape(-1) if data.get("f_fake") is not None else None
+
+
+def _mean(total, count):
+    return total / count if count > 0 else float("nan")          # torch.mean of an empty selection
+
+
+class _Evaluator(object):
+    valid_metrics = []
+
+    def _check_metrics(self, metrics):
+        for m in metrics:
+            assert m in self.valid_metrics
+
+    def _need_fake(self, fake):
+        if fake is None:
+            raise MissingFakeScores("the collector holds no 'f_fake'")
+
+
+class ContSurv_Evaluator(_Evaluator):
+    """Performance evaluator for continuous survival model"""
+
+    def __init__(self, **kws):
+        self.kws = kws
+        self.end_time = kws["end_time"]
+        self.valid_metrics = ["c_index", "loss_rank", "loss_recon", "loss_recon_org", "loss_fake_netD", "loss_fake_netG",
+                              "avg_fake", "event_t_rae", "nonevent_t_rae", "event_t_nre", "nonevent_t_nre", "mae"]
+
+    def compute(self, data, metrics):
+        self._check_metrics(metrics)
+        dev = _device_of(data)
+        L = _lib.lib()
+        y = _f32(data["y"], dev)
+        t, e = y[:, 0].contiguous(), y[:, 1].contiguous()
+        pred = _f32(data["avg_y_hat"] if "avg_y_hat" in data else data["y_hat"], dev).reshape(-1)
+        fake = _fake_of(data, dev)
+        n = t.numel()
+        kws = self.kws
+        recon = _recognise(kws["recon_loss"], LU.recon_loss, ("alpha", "gamma", "norm", "cur_alpha")) if _given(kws, "recon_loss") else None
+        rank = _recognise(kws["rank_loss"], LU.rank_loss, ("gamma", "norm", "add_weight")) if _given(kws, "rank_loss") else None
+        which, disc_fn = _disc_which(kws)
+        rc = recon or {}
+        alpha = rc.get("alpha", 0.0) if rc.get("cur_alpha") is None else rc["cur_alpha"]
+        res = torch.empty(_NRES, dtype=torch.float64, device=dev)
+        wsb = L.advmil_surv_metrics_cont_workspace_bytes(n)
+        ws = _ws(wsb, dev)
+        _lib.check(L.advmil_surv_metrics_cont(_p(t), _p(e), _p(pred), _p(fake), n, float(alpha), float(rc.get("gamma", 1.0)),
+                                              int(rc.get("norm", "l1") == "l2"), float(self.end_time), which or 0, _p(res), _p(ws), wsb,
+                                              _stream(dev)), "surv_metrics_cont")
+        if rank is not None and "loss_rank" in metrics:
+            LU._rank_loss_launch(pred, t, e, rank.get("gamma", 1), rank.get("norm", "l1"), rank.get("add_weight", False), res[_RANK:_RANK + 4])
+        r = res.cpu().tolist()                                   # the one device-to-host copy
+        n_evt, n_non = r[9], r[10]
+        out = dict()
+        for m in metrics:
+            if m == "c_index":
+                out[m] = concordance_index(y, pred.reshape(-1, 1))
+            elif m == "loss_rank":
+                out[m] = 0 if not _given(kws, "rank_loss") else (r[_RANK] if rank is not None else kws["rank_loss"](pred, t, e).item())
+            elif m == "loss_recon":
+                out[m] = 0 if not _given(kws, "recon_loss") else (r[0] / n if recon is not None else kws["recon_loss"](pred, t, e).item())
+            elif m == "loss_recon_org":
+                out[m] = 0 if not _given(kws, "recon_loss") else (
+                    r[1] / n if recon is not None else kws["recon_loss"](pred, t, e, cur_alpha=0.0).item())
+            elif m == "mae":
+                out[m] = r[2] / n
+            elif m == "loss_fake_netD":
+                if not _given(kws, "disc_loss"):
+                    out[m] = 0
+                else:
+                    self._need_fake(fake)
+                    out[m] = r[3] / n if disc_fn is None else disc_fn(None, fake).item()
+            elif m == "loss_fake_netG":
+                self._need_fake(fake)
+                out[m] = -r[4] / n
+            elif m == "avg_fake":
+                self._need_fake(fake)
+                out[m] = r[4] / n
+            elif m == "event_t_rae":
+                out[m] = _mean(r[5], n_evt)
+            elif m == "nonevent_t_rae":
+                out[m] = _mean(r[6], n_non)
+            elif m == "event_t_nre":
+                out[m] = _mean(r[7], n_evt)
+            elif m == "nonevent_t_nre":
+                out[m] = _mean(r[8], n_non)
+        return out
+
+
+class DiscSurv_Evaluator(_Evaluator):
+    """Evaluator of a discrete-time model: y[:, 0] is the bin index, y_hat the hazards [n, bins]."""
+
+    def __init__(self, **kws):
+        self.kws = kws
+        self.valid_metrics = ["c_index", "loss_mle", "loss_mle_org", "loss_fake_netD", "loss_fake_netG", "avg_fake"]
+
+    def compute(self, data, metrics):
+        self._check_metrics(metrics)
+        dev = _device_of(data)
+        L = _lib.lib()
+        y = _f32(data["y"], dev)
+        t, e = y[:, 0].contiguous(), y[:, 1].contiguous()
+        hz = _f32(data["avg_y_hat"] if "avg_y_hat" in data else data["y_hat"], dev)
+        hz = hz.reshape(hz.shape[0], -1)
+        fake = _fake_of(data, dev)
+        n, bins = hz.shape
+        kws = self.kws
+        mle = kws.get("mle_loss")
+        fused = type(mle) is LU.SurvMLE
+        which, disc_fn = _disc_which(kws)
+        res = torch.empty(_NRES, dtype=torch.float64, device=dev)
+        risk = torch.empty(n, dtype=torch.float32, device=dev)
+        wsb = L.advmil_surv_metrics_disc_workspace_bytes(n)
+        ws = _ws(wsb, dev)
+        if not 1 <= bins <= 256:
+            raise ValueError(f"DiscSurv_Evaluator: {bins} bins; the HIP path takes 1 to 256")
+        _lib.check(L.advmil_surv_metrics_disc(_p(hz), hz.stride(0), _p(t), _p(e), _p(fake), n, bins, float(mle.alpha) if fused else 0.0,
+                                              float(mle.eps) if fused else 1e-7, which or 0, _p(risk), _p(res), _p(ws), wsb, _stream(dev)),
+                   "surv_metrics_disc")
+        r = res.cpu().tolist()                                   # the one device-to-host copy
+        if r[4] != 0:
+            raise ValueError(f"DiscSurv_Evaluator: {int(r[4])} of {n} samples carry a bin index outside [0, {bins - 1}]")
+        out = dict()
+        for m in metrics:
+            if m == "c_index":
+                # (one bin: the reference's concordance_index takes an [n, 1] prediction for a time, not for hazards -- eval/cindex.py:34-36)
+                out[m] = concordance_index(y, hz) if bins == 1 else concordance_index_censored(e, t, -risk, tied_tol=1e-08, device=dev)[0]
+            elif m == "loss_mle":
+                assert "mle_loss" in kws
+                out[m] = r[0] / n if fused else mle(hz, t, e).item()
+            elif m == "loss_mle_org":
+                assert "mle_loss" in kws
+                out[m] = r[1] / n if fused else mle(hz, t, e, cur_alpha=0.0).item()
+            elif m == "loss_fake_netD":
+                if not _given(kws, "disc_loss"):
+                    out[m] = 0
+                else:
+                    self._need_fake(fake)
+                    out[m] = r[2] / n if disc_fn is None else disc_fn(None, fake).item()
+            elif m == "loss_fake_netG":
+                self._need_fake(fake)
+                out[m] = -r[3] / n
+            elif m == "avg_fake":
+                self._need_fake(fake)
+                out[m] = r[3] / n
+        return out
+
+
+class CoxSurv_Evaluator(_Evaluator):
+    """Performance evaluator for Cox-based survival model"""
+
+    def __init__(self, **kws):
+        self.kws = kws
+        self.valid_metrics = ["c_index", "loss_ple"]
+
+    def compute(self, data, metrics):
+        self._check_metrics(metrics)
+        dev = _device_of(data)
+        L = _lib.lib()
+        y = _f32(data["y"], dev)
+        t, e = y[:, 0].contiguous(), y[:, 1].contiguous()
+        pred = _f32(data["avg_y_hat"] if "avg_y_hat" in data else data["y_hat"], dev).reshape(-1)
+        n = t.numel()
+        kws = self.kws
+        fused = type(kws.get("ple_loss")) is LU.SurvPLE
+        r = None
+        if fused and "loss_ple" in metrics:
+            res = torch.empty(_NRES, dtype=torch.float64, device=dev)
+            wsb = L.advmil_ple_loss_workspace_bytes(n)
+            ws = _ws(wsb, dev)
+            _lib.check(L.advmil_ple_loss(_p(pred), _p(t), _p(e), n, _p(res[_PLE:_PLE + 2]), _p(ws), wsb, _stream(dev)), "ple_loss")
+            r = res[_PLE:_PLE + 2].cpu().tolist()                # the one device-to-host copy
+        out = dict()
+        for m in metrics:
+            if m == "c_index":
+                out[m] = concordance_index(y, pred.reshape(-1, 1))
+            elif m == "loss_ple":
+                out[m] = 0 if not _given(kws, "ple_loss") else (r[0] if fused else kws["ple_loss"](pred, t, e).item())
+        return out

@@ -1,8 +1,11 @@
-"""Losses of the G+D step (reference loss/utils.py): loss_reg_l1 (6-14), recon_loss (21-41),
+"""Losses of the G+D step (reference loss/utils.py): loss_reg_l1 (6-14), recon_loss (21-41), rank_loss (43-80),
 real_fake_loss (182-203), fake_generator_loss (205-208); and of the supervised baselines: MSE_loss (82-96), SurvMLE (99-135),
 SurvPLE (138-175). They act on <= bp_every_batch scalars, so
 they are a handful of tiny device ops; the one N-sized piece -- sum|W| over the generator arena -- is
-the abs_sum kernel, and its gradient is folded into the fused Adam kernel (advmil_amd/optim.py)."""
+the abs_sum kernel, and its gradient is folded into the fused Adam kernel (advmil_amd/optim.py). rank_loss is O(n^2) in the number
+of samples: its forward and backward are the pair kernels advmil_rank_loss_fwd / _bwd (csrc/survk.hip), with no n x n matrix."""
+import ctypes
+
 import torch
 import torch.nn.functional as F
 
@@ -34,6 +37,68 @@ def recon_terms(pred_t, t, e, alpha=0.0, gamma=1.0, norm="l1", cur_alpha=None):
 
 def recon_loss(pred_t, t, e, alpha=0.0, gamma=1.0, norm="l1", cur_alpha=None):
     return recon_terms(pred_t, t, e, alpha, gamma, norm, cur_alpha).mean()
+
+
+def _vp(t):
+    return ctypes.c_void_p(t.data_ptr())
+
+
+def _rank_loss_launch(pred_t, t, e, gamma, norm, add_weight, state=None):
+    """advmil_rank_loss_fwd on contiguous fp32 device vectors -> (loss [0-dim fp32], state [4 doubles]: loss, #pairs | Z, max, #pairs)."""
+    from .. import _lib
+    if norm not in ("l1", "l2"):
+        raise NotImplementedError('Arg. `norm` expected l1/l2, but got {}'.format(norm))
+    L = _lib.lib()
+    n, dev = pred_t.numel(), pred_t.device
+    if state is None:
+        state = torch.empty(4, dtype=torch.float64, device=dev)
+    loss = torch.empty((), dtype=torch.float32, device=dev)
+    wsb = L.advmil_rank_loss_workspace_bytes(n)
+    ws = torch.empty((wsb + 7) // 8, dtype=torch.float64, device=dev)
+    _lib.check(L.advmil_rank_loss_fwd(_vp(pred_t), _vp(t), _vp(e), n, float(gamma), int(norm == "l2"), int(bool(add_weight)), _vp(state),
+                                      _vp(loss), _vp(ws), wsb, ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "rank_loss_fwd")
+    return loss, state
+
+
+class _RankLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, pred_t, t, e, gamma, norm, add_weight):
+        loss, state = _rank_loss_launch(pred_t, t, e, gamma, norm, add_weight)
+        ctx.save_for_backward(pred_t, t, e, state)
+        ctx.cfg = (float(gamma), int(norm == "l2"), int(bool(add_weight)))
+        return loss
+
+    @staticmethod
+    def backward(ctx, gout):
+        from .. import _lib
+        pred_t, t, e, state = ctx.saved_tensors
+        gamma, l2, add_weight = ctx.cfg
+        dev = pred_t.device
+        gout = gout.to(device=dev, dtype=torch.float32).contiguous()
+        dpred = torch.empty_like(pred_t)
+        _lib.check(_lib.lib().advmil_rank_loss_bwd(_vp(pred_t), _vp(t), _vp(e), pred_t.numel(), gamma, l2, add_weight, _vp(state), _vp(gout),
+                                                   _vp(dpred), ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "rank_loss_bwd")
+        return dpred, None, None, None, None, None
+
+
+def rank_loss(pred_t, t, e, gamma=1, norm="l1", add_weight=False):
+    """loss/utils.py:43-80: over the pairs (i, j) with e_i == 1 and t_i < t_j, relu(gamma + pred_i - pred_j) (squared for l2), averaged
+    with uniform weights or, with `add_weight`, with the softmax of pred_i - pred_j over the pairs. Differentiable in `pred_t` only.
+    Differences from the reference, both so that no host read is needed: the result is a 0-dim tensor in EVERY case (the reference returns
+    shape [1] when there is no pair; the value is 0 and the gradient all zeros here too), and a `norm` other than l1 / l2 raises
+    NotImplementedError whether or not there is a pair. Device tensors only."""
+    if norm not in ("l1", "l2"):
+        raise NotImplementedError('Arg. `norm` expected l1/l2, but got {}'.format(norm))
+    if not torch.cuda.is_available():
+        raise RuntimeError("advmil_amd.loss.utils.rank_loss needs an MI355X: no ROCm device visible (no CPU fallback)")
+    ops._chk(pred_t, "pred_t")
+    dev = pred_t.device
+    p = pred_t.reshape(-1).to(torch.float32).contiguous()
+    t = t.detach().reshape(-1).to(device=dev, dtype=torch.float32).contiguous()
+    e = e.detach().reshape(-1).to(device=dev, dtype=torch.float32).contiguous()
+    if not (p.numel() == t.numel() == e.numel()) or p.numel() == 0:
+        raise ValueError("rank_loss: pred_t, t and e must hold the same, non-zero number of samples")
+    return _RankLoss.apply(p, t, e, gamma, norm, add_weight)
 
 
 def real_fake_terms(real, fake, which="bce"):

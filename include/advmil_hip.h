@@ -594,6 +594,46 @@ int advmil_gan_g_loss(const float* pred, const float* t, const float* e, const f
 int advmil_cindex_counts(const float* time, const float* event, const float* estimate, int64_t n, float tied_tol, int64_t* out6,
                          advmil_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Survival evaluators (eval/evaluator.py:11,133,213) and the two O(n^2) pair losses (loss/utils.py:43-80, 155-175), csrc/survk.hip.
+ * fp32 inputs; every term is formed in fp32 (exp / log of a term: the hardware v_exp_f32 / v_log_f32, ~1 ulp), every sum is carried
+ * in double; per-anchor logs and the rescaling of the softmax merge are double-precision libm. No floating-point atomics: partials go
+ * to `ws` (>= the matching *_workspace_bytes(n), pure host functions) and a second launch merges them in a fixed order, so results
+ * are bit-reproducible and independent of what `ws` and the outputs held. Every output slot is written. Asynchronous on `stream`,
+ * capturable. 1 <= n <= 2^31 - 1. `which`: 0 bce as shipped | 1 hinge | 2 wasserstein (as advmil_gan_d_loss); `fake` may be NULL
+ * (its slots are then 0).
+ *
+ * advmil_surv_metrics_cont -> out16 (device, double): 0 sum of recon_loss terms at `alpha`, 1 at alpha = 0, 2 sum of the `mae` terms
+ *   (recon_loss defaults: gamma 1, l1, alpha 0), 3 sum of the discriminator's fake-only terms, 4 sum fake,
+ *   5 sum_{e==1} |t-p| / end_time, 6 sum_{e==0} relu(t-p) / end_time, 7 sum_{e==1} (p-t) / end_time, 8 sum_{e==0} -relu(t-p) / end_time,
+ *   9 #(e == 1), 10 #(e == 0), 11..15 zero. The caller forms the means.
+ * advmil_surv_metrics_disc: hazards[n, bins] with row pitch ld (elements), 1 <= bins <= 256; t = bin index carried as fp32 (truncated
+ *   toward zero). risk[n] = sum_k prod_{l<=k} (1 - h_l). out16: 0 sum of SurvMLE terms (loss/utils.py:123-133, both clamps at eps) at
+ *   `alpha`, 1 at alpha = 0, 2 sum of fake-only terms, 3 sum fake, 4 number of rows whose bin index lies outside [0, bins-1] (such an
+ *   index is never used as an address; the row adds nothing to slots 0-1), 5..15 zero.
+ * advmil_ple_loss: SurvPLE.forward for 1-D T, E: out2[0] = -mean_i (theta_i - log sum_j [T_j >= T_i] exp theta_j) E_i with theta
+ *   clamped at 10, out2[1] = sum E.
+ * advmil_rank_loss_fwd: pairs (i, j) with t_i < t_j and e_i == 1, x = p_i - p_j, L = relu(gamma + x) (squared if l2); weights 1/#pairs
+ *   or, with add_weight, softmax of x over the pairs. loss[0] (fp32) and state4 (double) = loss, #pairs or Z, max x (0 for uniform
+ *   weights), #pairs. No pair: loss 0.
+ * advmil_rank_loss_bwd: dpred[k] = gout[0] * (sum_j dx_kj - sum_i dx_ik), dx = w L' (uniform) or w (L' + L - loss) (softmax weights),
+ *   from the forward's state4; no pair: all zeros. */
+size_t advmil_surv_metrics_cont_workspace_bytes(int64_t n);
+int advmil_surv_metrics_cont(const float* t, const float* e, const float* pred, const float* fake, int64_t n, float alpha, float gamma,
+                             int l2, float end_time, int which, double* out16, void* ws, size_t ws_bytes, advmil_stream_t stream);
+size_t advmil_surv_metrics_disc_workspace_bytes(int64_t n);
+int advmil_surv_metrics_disc(const float* hazards, int64_t ld, const float* t, const float* e, const float* fake, int64_t n, int bins,
+                             float alpha, float eps, int which, float* risk, double* out16, void* ws, size_t ws_bytes,
+                             advmil_stream_t stream);
+size_t advmil_ple_loss_workspace_bytes(int64_t n);
+int advmil_ple_loss(const float* theta, const float* T, const float* E, int64_t n, double* out2, void* ws, size_t ws_bytes,
+                    advmil_stream_t stream);
+size_t advmil_rank_loss_workspace_bytes(int64_t n);
+int advmil_rank_loss_fwd(const float* pred, const float* t, const float* e, int64_t n, float gamma, int l2, int add_weight,
+                         double* state4, float* loss, void* ws, size_t ws_bytes, advmil_stream_t stream);
+int advmil_rank_loss_bwd(const float* pred, const float* t, const float* e, int64_t n, float gamma, int l2, int add_weight,
+                         const double* state4, const float* gout, float* dpred, advmil_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
