@@ -108,7 +108,66 @@ __global__ __launch_bounds__(256) void surv_merge_kernel(const double* __restric
 // The bin index selects by COMPARISON inside the walk over the row (k == bin), never as an address; a row whose index is outside
 // [0, bins - 1] (or not a number) contributes nothing and is counted in slot 4.
 //  0 sum SurvMLE terms at alpha   1 ... at alpha = 0   2 sum fake-only discriminator terms   3 sum fake   4 #rows with a bad bin index
+//
+// The risk is the reference's float32 number BIT FOR BIT: it goes, negated, into the concordance index, where a pair is a tie only
+// within 1e-8, so a last-bit difference moves pairs between "tied" and "ordered" whenever two rows hold the same hazards in another
+// order (quantised or saturating hazards). The reference forms it as np.sum(np.cumprod(1 - h, axis=1), axis=1) in float32, hence
+//  - 1 - h, the running product and every addition are single rounded operations (no contraction into v_fma / v_fmac);
+//  - the additions follow numpy's pairwise sum over a contiguous row: fewer than 8 elements in order; up to 128 elements eight
+//    accumulators r[j] = a[j], r[j] += a[i + j] for i = 8, 16, ... < n - n % 8, then ((r0+r1)+(r2+r3))+((r4+r5)+(r6+r7)) and the
+//    last n % 8 elements in order; above 128 a split at n2 = n / 2 - (n / 2) % 8, both halves by the same rule, left + right.
+// For bins <= 256 that is at most three leaves, A | B or A | (B1 | B2), walked in one pass over the row.
 // ---------------------------------------------------------------------------------------------------------------------------------
+#pragma clang fp contract(off)
+struct DiscRowWalk {                                            // the running product over one row and what SurvMLE gathers from it
+  const float* row;
+  int bin, k;
+  float S, S_prev, S_at, h_at;
+  __host__ __device__ __forceinline__ float next() {            // -> S_k, and steps to k + 1
+    const float h = row[k];
+    const float om = 1.0f - h;
+    const float Sn = S * om;
+    if (k == bin) { S_prev = S; S_at = Sn; h_at = h; }
+    S = Sn;
+    ++k;
+    return Sn;
+  }
+};
+
+// numpy's pairwise leaf (len <= 128) over the next `len` elements of the walk
+__host__ __device__ __forceinline__ float np_leaf_sum(DiscRowWalk& w, int len) {
+  if (len < 8) {
+    float res = 0.0f;
+    for (int i = 0; i < len; ++i) res = res + w.next();
+    return res;
+  }
+  float r0 = w.next(), r1 = w.next(), r2 = w.next(), r3 = w.next(), r4 = w.next(), r5 = w.next(), r6 = w.next(), r7 = w.next();
+  const int body = len - len % 8;
+  for (int i = 8; i < body; i += 8) {
+    r0 = r0 + w.next(); r1 = r1 + w.next(); r2 = r2 + w.next(); r3 = r3 + w.next();
+    r4 = r4 + w.next(); r5 = r5 + w.next(); r6 = r6 + w.next(); r7 = r7 + w.next();
+  }
+  float res = ((r0 + r1) + (r2 + r3)) + ((r4 + r5) + (r6 + r7));
+  for (int i = body; i < len; ++i) res = res + w.next();
+  return res;
+}
+
+// np.sum over the `n` <= 256 elements of the walk
+__host__ __device__ __forceinline__ float np_row_sum(DiscRowWalk& w, int n) {
+  if (n <= 128) return np_leaf_sum(w, n);
+  int n2 = n / 2;
+  n2 -= n2 % 8;
+  const float left = np_leaf_sum(w, n2);
+  const int nr = n - n2;                                        // <= 135
+  if (nr <= 128) return left + np_leaf_sum(w, nr);
+  int m = nr / 2;
+  m -= m % 8;
+  const float b1 = np_leaf_sum(w, m);
+  const float b2 = np_leaf_sum(w, nr - m);
+  return left + (b1 + b2);
+}
+#pragma clang fp contract(fast)
+
 __global__ __launch_bounds__(256) void surv_disc_partial_kernel(const float* __restrict__ hz, int64_t ld, const float* __restrict__ t,
                                                                 const float* __restrict__ e, const float* __restrict__ fake,
                                                                 int64_t n, int bins, float alpha, float eps, int which,
@@ -118,16 +177,9 @@ __global__ __launch_bounds__(256) void surv_disc_partial_kernel(const float* __r
     const float tf = truncf(t[i]);                        // .long() of the reference truncates toward zero
     const bool ok = tf >= 0.0f && tf <= (float)(bins - 1);
     const int bin = ok ? (int)tf : -1;
-    const float* row = hz + i * ld;
-    float S = 1.0f, S_prev = 1.0f, S_at = 1.0f, h_at = 1.0f, rsum = 0.0f;
-    for (int k = 0; k < bins; ++k) {
-      const float h = row[k];
-      const float Sn = S * (1.0f - h);
-      if (k == bin) { S_prev = S; S_at = Sn; h_at = h; }
-      S = Sn;
-      rsum += Sn;
-    }
-    risk[i] = rsum;
+    DiscRowWalk w{hz + i * ld, bin, 0, 1.0f, 1.0f, 1.0f, 1.0f};
+    risk[i] = np_row_sum(w, bins);
+    const float S_prev = w.S_prev, S_at = w.S_at, h_at = w.h_at;
     if (ok) {
       const float ei = e[i], c = 1.0f - ei;
       const float unc = -(1.0f - c) * (hw_log(fmaxf(S_prev, eps)) + hw_log(fmaxf(h_at, eps)));

@@ -17,6 +17,7 @@ from oracle import cindex_oracle as CO
 from tests.golden import gen_golden_evaluator as G
 
 GOLD = json.load(open(G.FIXTURE))
+GOLD2 = json.load(open(G.FIXTURE2))      # quantised / saturating hazards (discrete only)
 TOL = 2e-5
 
 
@@ -153,6 +154,30 @@ def test_restatement_reproduces_the_reference_discrete(k):
     assert y[:, 0].min() >= 0 and y[:, 0].max() == G.DISC_CASES[k]["bins"] - 1
 
 
+@pytest.mark.parametrize("k", range(len(G.DISC2_CASES)))
+def test_restatement_reproduces_the_reference_discrete_with_quantised_hazards(k):
+    y, hz, fake = G.disc2_inputs(k)
+    c, gold = G.DISC2_CASES[k], GOLD2["discrete"][k]
+    assert set(gold) == set(want_disc(y, hz, fake, c)) | {"c_index"}
+    for m, v in want_disc(y, hz, fake, c).items():
+        assert close(v, gold[m]), (k, m, v, gold[m])
+    assert abs(CO.concordance_index(y, hz) - gold["c_index"]) < 1e-12
+    assert hz.shape == (300, c["bins"]) and y[:, 0].min() >= 0 and y[:, 0].max() <= c["bins"] - 1
+    if c["levels"] is not None:
+        assert set(np.unique(hz).tolist()) == {float(np.float32(v)) for v in c["levels"]}
+
+
+def test_quantised_fixture_is_sensitive_to_a_fused_left_to_right_risk():
+    """The precondition gen_golden_evaluator.main() asserts against the reference, restated on the oracle: in at least four of the six
+    cases the c-index moves when numpy's risk is replaced by a left-to-right sum with one fused multiply-add per bin."""
+    moved = 0
+    for k in range(len(G.DISC2_CASES)):
+        y, hz, _ = G.disc2_inputs(k)
+        fused = CO.cindex_counts(y[:, 1].astype(bool), y[:, 0], -G.fused_left_to_right_risk(hz))[0]
+        moved += int(abs(fused - GOLD2["discrete"][k]["c_index"]) >= 1e-12)
+    assert moved >= G.DISC2_MIN_SENSITIVE, moved
+
+
 @pytest.mark.parametrize("k", range(len(G.COX_CASES)))
 def test_restatement_reproduces_the_reference_cox(k):
     y, theta = G.cox_inputs(k)
@@ -161,6 +186,46 @@ def test_restatement_reproduces_the_reference_cox(k):
     assert abs(CO.concordance_index(y, theta) - gold["c_index"]) < 1e-12
     if k == 0:
         assert float(theta.max()) > 10.0 and len(np.unique(y[:, 0])) == len(y)
+
+
+# ---- 1b. the fixed-seed leg of tools/probe/surv_fuzz.py, replayed without a device -------------------------------------------------
+def test_surv_fuzz_fixed_seed_leg_draws_every_kind_and_leaves_out_few():
+    """The draws of `surv_fuzz.py 12 110` (tests/test_fuzz_gpu.py): every family meets each of its kinds, the cohorts span what the
+    probe promises, and the share of rank_loss draws left out for a hinge within 1e-6 of its kink stays under the probe's cap."""
+    import importlib.util
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    assert '("surv_fuzz.py", ("12", "110"))' in open(os.path.join(root, "tests", "test_fuzz_gpu.py")).read()
+    spec = importlib.util.spec_from_file_location("surv_fuzz", os.path.join(root, "tools", "probe", "surv_fuzz.py"))
+    F = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(F)
+    cases = F.draws(12, 110)
+    assert list(cases) == list(F.FAMILIES) and all(len(v) == 12 for v in cases.values())
+    again = F.draws(12, 110)
+    for fam in F.FAMILIES:
+        assert {d["kind"] for d in cases[fam]} == set(F.KINDS[fam]), fam
+        assert all(1 <= d["n"] <= 1500 for d in cases[fam])
+        for a, b in zip(cases[fam], again[fam]):                   # the same draws on every machine
+            assert all(np.array_equal(a[k], b[k]) if isinstance(a[k], np.ndarray) else a[k] == b[k] for k in a)
+    every = [d for v in cases.values() for d in v]
+    assert {0.0, 1.0} <= {d["event_share"] for d in every} and {0, 3, 50} == {d["time_levels"] for d in every}
+    assert {0, 40} == {d["est_levels"] for d in cases["cont"]} and any(d["fake"] is None for d in cases["cont"])
+    assert {0.0, 0.3, 1.0} == {d["alpha"] for d in cases["cont"]} == {d["alpha"] for d in cases["disc"]}
+    assert min(d["bins"] for d in cases["disc"]) < 8 and max(d["bins"] for d in cases["disc"]) > 128 and {0, 3} == {d["pad"] for d in cases["disc"]}
+    assert all(float(d["theta"].min()) >= -12.0 and float(d["theta"].max()) <= 14.0 for d in cases["ple"])
+    assert any(float(d["theta"].max()) > 10.0 for d in cases["ple"])
+    ranks = cases["rank_fwd"] + cases["rank_bwd"]
+    assert {"fine", "sixtyfourths", "fortieths"} == {d["grid"] for d in ranks} and {1.0, 16.0} == {d["scale"] for d in ranks}
+    margins = [F.want_rank(d)[2] for d in ranks]
+    skipped = sum(F.left_out(d, m) for d, m in zip(ranks, margins))
+    assert skipped <= F.MAX_SKIPPED * len(ranks), (skipped, len(ranks))
+    assert sum(math.isfinite(m) for m in margins) >= len(ranks) // 2          # most draws do hold pairs
+    # the float64 sides answer on every draw
+    for d in cases["cont"]:
+        assert all(v is None or math.isfinite(v) for v in F.want_cont(d)[0])
+    for d in cases["disc"]:
+        want, risk = F.want_disc(d)
+        assert all(math.isfinite(v) for v in want) and risk.dtype == np.float32 and risk.shape == (d["n"],)
+    assert all(math.isfinite(F.want_ple(d)) for d in cases["ple"])
 
 
 # ---- 2. public surface ----------------------------------------------------------------------------------------------------------

@@ -10,7 +10,7 @@ import torch
 
 from tests.golden import gen_golden_evaluator as G
 from tests.poison import assert_same_bits, three_runs
-from tests.test_evaluator_cpu import GOLD, TOL, close
+from tests.test_evaluator_cpu import GOLD, GOLD2, TOL, close
 
 pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda", 0)
@@ -66,6 +66,15 @@ def test_discrete_golden_cases(k):
     from advmil_amd.eval import prepare_evaluator
     y, hz, fake = G.disc_inputs(k)
     check_against(prepare_evaluator("discrete", **disc_kws(G.DISC_CASES[k])), {"y": T(y), "y_hat": T(hz), "f_fake": T(fake)}, GOLD["discrete"][k])
+
+
+@pytest.mark.parametrize("k", range(len(G.DISC2_CASES)))
+def test_discrete_golden_cases_with_quantised_hazards(k):
+    """tests/golden/evaluator_v2.json: rows that hold the same few hazard levels in another order. The c-index at 1e-12 needs the
+    kernel's risk to be the reference's float32 number bit for bit (numpy's pairwise order, no contraction)."""
+    from advmil_amd.eval import prepare_evaluator
+    y, hz, fake = G.disc2_inputs(k)
+    check_against(prepare_evaluator("discrete", **disc_kws(G.DISC2_CASES[k])), {"y": T(y), "y_hat": T(hz), "f_fake": T(fake)}, GOLD2["discrete"][k])
 
 
 @pytest.mark.parametrize("k", range(len(G.COX_CASES)))

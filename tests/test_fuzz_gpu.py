@@ -16,7 +16,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 @pytest.mark.timeout(900)
 @pytest.mark.parametrize("script,args", [("gemm_fuzz.py", ("80", "101")), ("attn_fuzz.py", ("24", "102")), ("pool_fuzz.py", ("40", "103")),
                                          ("graph_fuzz.py", ("40", "104")), ("misc_fuzz.py", ("10", "105")), ("oracle_fuzz.py", ("8", "106")),
-                                         ("pad_fuzz.py", ("1", "107")), ("dp_fuzz.py", ("2", "108")), ("baseline_fuzz.py", ("6", "109"))])
+                                         ("pad_fuzz.py", ("1", "107")), ("dp_fuzz.py", ("2", "108")), ("baseline_fuzz.py", ("6", "109")),
+                                         ("surv_fuzz.py", ("12", "110"))])
 def test_randomised_probe(script, args):
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     env["ADVMIL_GEMM_MODE"] = "exact"          # the probes' starting arithmetic (those that cover bf16x3 select it themselves)
