@@ -65,6 +65,19 @@ class GHead(ctypes.Structure):
                 ("ws", c_void_p), ("ws_bytes", c_size_t)]
 
 
+class Optim(ctypes.Structure):
+    """advmil_optim_t"""
+    _fields_ = [("kind", ctypes.c_int32), ("lookahead", ctypes.c_int32), ("n", c_int64), ("p", c_void_p), ("grad", c_void_p),
+                ("s1", c_void_p), ("s2", c_void_p), ("wd", c_void_p), ("slow", c_void_p), ("lr", ctypes.c_double),
+                ("beta1", ctypes.c_double), ("beta2", ctypes.c_double), ("eps", ctypes.c_double), ("schedule_decay", ctypes.c_double),
+                ("grad_scale", c_float), ("l1_coef", c_float), ("la_alpha", c_float), ("la_k", ctypes.c_int32), ("tick", ctypes.c_int32),
+                ("step", c_void_p), ("la_state", c_void_p), ("m_sched", c_void_p), ("p_hi", c_void_p), ("p_lo", c_void_p),
+                ("abs_partial", c_void_p), ("clear_grad", ctypes.c_int32)]
+
+
+OPT_KINDS = {"adam": 0, "adamw": 1, "nadam": 2, "radam": 3, "adadelta": 4}       # ADVMIL_OPT_*
+
+
 # name -> (restype, argtypes); must list every symbol include/advmil_hip.h declares
 SIGNATURES = {
     "advmil_version": (c_int, []),
@@ -143,6 +156,7 @@ SIGNATURES = {
     "advmil_adam_step": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_float, c_float, c_float,
                                  c_float, c_float, c_float, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p]),
     "advmil_adam_blocks": (c_int, [c_int64]),
+    "advmil_optim_step": (c_int, [ctypes.POINTER(Optim), c_void_p]),
     "advmil_step_seed_tick": (c_int, [c_void_p, c_void_p, c_void_p, c_uint64, c_void_p]),
     "advmil_abs_sum": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_size_t, c_void_p]),
     "advmil_abs_sum_workspace_bytes": (c_size_t, [c_int64]),

@@ -116,6 +116,188 @@ extern "C" int advmil_step_seed_tick(int32_t* step, int32_t* step2, uint64_t* se
   return ADVMIL_OK;
 }
 
+// =====================================================================================
+// The other elementwise optimizers of optim/optim_factory.py (AdamW, NAdam, RAdam, Adadelta; Adam again as the base of
+// lookahead_adam), optionally behind optim/lookahead.py -- same arenas, access pattern and options as adam_kernel, which stays as it is.
+// =====================================================================================
+// What one launch needs beyond the element's own values: the fp32 constants of the update and the step-dependent scalars.
+struct OptK {
+  float lr, b1, omb1, b2, omb2, eps, gscale, l1;
+  float a, b, c;     // ADAM/ADAMW: a = lr/(1-b1^t), b = 1/sqrt(1-b2^t); NADAM: a, c = the factors of g and m, b as before; RADAM: a = step size
+  int rect;          // RADAM: N_sma >= 5
+};
+// Evaluated in double inside the launch, by every thread: b2^t must be good to ~1e-10 for RAdam (N_sma = 1999 - (a number near 1994)
+// around the N_sma >= 5 threshold) and NAdam's schedule is a running product, so the hardware exp2/log2 of adam_kernel will not do.
+// A one-thread prologue launch would put a whole launch (~4 us, see adam_kernel) and a round trip through memory in front of this one;
+// the two exp and two log in double cost about a third of that. It is their latency, not the double-precision pipe: having only the
+// first wave of a workgroup evaluate them and hand them over through LDS measured the same, so the plain form stays (numbers:
+// docs/DESIGN_HISTORY.md section G).
+template <int KIND>
+__device__ __forceinline__ OptK opt_scalars(const advmil_optim_t& o, int t) {
+  OptK k;
+  k.lr = (float)o.lr; k.b1 = (float)o.beta1; k.omb1 = (float)(1.0 - o.beta1); k.b2 = (float)o.beta2; k.omb2 = (float)(1.0 - o.beta2);
+  k.eps = (float)o.eps; k.gscale = o.grad_scale; k.l1 = o.l1_coef;
+  k.a = k.b = k.c = 0.f; k.rect = 0;
+  if (KIND == ADVMIL_OPT_ADADELTA) return k;
+  const double td = (double)t;
+  const double b1t = exp(td * log(o.beta1)), b2t = exp(td * log(o.beta2));
+  if (KIND == ADVMIL_OPT_ADAM || KIND == ADVMIL_OPT_ADAMW) {
+    k.a = (float)(o.lr / (1.0 - b1t));
+    k.b = (float)(1.0 / sqrt(1.0 - b2t));
+  } else if (KIND == ADVMIL_OPT_NADAM) {
+    const double l96 = log(0.96) * o.schedule_decay;
+    const double mu_t = o.beta1 * (1.0 - 0.5 * exp(td * l96)), mu_t1 = o.beta1 * (1.0 - 0.5 * exp((td + 1.0) * l96));
+    const double ms_new = o.m_sched[(t - 1) & 1] * mu_t, ms_next = ms_new * mu_t1;
+    k.a = (float)(o.lr * (1.0 - mu_t) / (1.0 - ms_new));
+    k.c = (float)(o.lr * mu_t1 / (1.0 - ms_next));
+    k.b = (float)(1.0 / sqrt(1.0 - b2t));
+    if (blockIdx.x == 0 && threadIdx.x == 0) o.m_sched[t & 1] = ms_new;      // (the other slot: nobody reads it in this launch)
+  } else {   // RADAM
+    const double nmax = 2.0 / (1.0 - o.beta2) - 1.0;
+    const double nsma = nmax - 2.0 * td * b2t / (1.0 - b2t);
+    k.rect = nsma >= 5.0;
+    k.a = k.rect ? (float)(o.lr * sqrt((1.0 - b2t) * (nsma - 4.0) / (nmax - 4.0) * (nsma - 2.0) / nsma * nmax / (nmax - 2.0)) / (1.0 - b1t))
+                 : (float)(o.lr / (1.0 - b1t));
+  }
+  return k;
+}
+template <int KIND>
+__device__ __forceinline__ float opt_elem(float w, float g0, float& s1, float& s2, float wdv, const OptK& k) {
+  float g = g0 * k.gscale;
+  if (k.l1 != 0.f) g += k.l1 * (w > 0.f ? 1.f : (w < 0.f ? -1.f : 0.f));
+  if (KIND == ADVMIL_OPT_ADADELTA) {
+    g += wdv * w;
+    s1 = k.b1 * s1 + k.omb1 * g * g;                                  // square_avg (rho = beta1)
+    const float delta = hw_sqrt(s2 + k.eps) * hw_rsq(s1 + k.eps) * g;
+    s2 = k.b1 * s2 + k.omb1 * delta * delta;                          // acc_delta
+    return w - k.lr * delta;
+  }
+  if (KIND == ADVMIL_OPT_ADAM || KIND == ADVMIL_OPT_NADAM) g += wdv * w;
+  if (KIND == ADVMIL_OPT_ADAMW) w *= 1.f - k.lr * wdv;
+  s1 = k.b1 * s1 + k.omb1 * g;
+  s2 = k.b2 * s2 + k.omb2 * g * g;
+  if (KIND == ADVMIL_OPT_RADAM) {
+    w -= wdv * k.lr * w;
+    return k.rect ? w - k.a * s1 * hw_rcp(hw_sqrt(s2) + k.eps) : w - k.a * s1;
+  }
+  const float r = hw_rcp(hw_sqrt(s2) * k.b + k.eps);
+  if (KIND == ADVMIL_OPT_NADAM) return w - (k.a * g + k.c * s1) * r;
+  return w - k.a * s1 * r;
+}
+// lookahead sync of one element: the sync that creates the slow buffer copies the fast weight into it (and so changes nothing)
+__device__ __forceinline__ float la_sync(float fast, float& slow, bool first, float alpha) {
+  slow = first ? fast : slow + alpha * (fast - slow);
+  return slow;
+}
+template <int KIND, bool LA>
+__global__ __launch_bounds__(256) void optim_kernel(const advmil_optim_t o) {
+  __shared__ float red[4];
+  float asum = 0.f;
+  const int t = *o.step + 1;                 // (bumped behind this kernel, as for adam_kernel)
+  const OptK k = opt_scalars<KIND>(o, t);
+  bool sync = false, first = false;
+  if (LA) {
+    const int lt = t - o.la_state[1];
+    sync = lt > 0 && lt % o.la_k == 0;
+    first = lt <= o.la_state[0];
+  }
+  float* __restrict__ p = o.p; float* __restrict__ grad = o.grad; float* __restrict__ s1 = o.s1; float* __restrict__ s2 = o.s2;
+  const float* __restrict__ wd = o.wd; float* __restrict__ slow = o.slow;
+  unsigned short* __restrict__ p_hi = (unsigned short*)o.p_hi; unsigned short* __restrict__ p_lo = (unsigned short*)o.p_lo;
+  const int64_t n = o.n, n4 = n >> 2;
+  for (int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q < n4; q += (int64_t)gridDim.x * blockDim.x) {
+    const float4 w4 = reinterpret_cast<const float4*>(p)[q], g4 = reinterpret_cast<const float4*>(grad)[q];
+    float4 m4 = reinterpret_cast<const float4*>(s1)[q], v4 = reinterpret_cast<const float4*>(s2)[q];
+    const float4 d4 = wd ? reinterpret_cast<const float4*>(wd)[q] : make_float4(0.f, 0.f, 0.f, 0.f);
+    if (o.clear_grad) reinterpret_cast<float4*>(grad)[q] = make_float4(0.f, 0.f, 0.f, 0.f);
+    asum += (fabsf(w4.x) + fabsf(w4.y)) + (fabsf(w4.z) + fabsf(w4.w));
+    float4 r;
+    r.x = opt_elem<KIND>(w4.x, g4.x, m4.x, v4.x, d4.x, k);
+    r.y = opt_elem<KIND>(w4.y, g4.y, m4.y, v4.y, d4.y, k);
+    r.z = opt_elem<KIND>(w4.z, g4.z, m4.z, v4.z, d4.z, k);
+    r.w = opt_elem<KIND>(w4.w, g4.w, m4.w, v4.w, d4.w, k);
+    reinterpret_cast<float4*>(s1)[q] = m4;
+    reinterpret_cast<float4*>(s2)[q] = v4;
+    if (LA && sync) {
+      float4 sl = first ? r : reinterpret_cast<const float4*>(slow)[q];
+      r.x = la_sync(r.x, sl.x, first, o.la_alpha); r.y = la_sync(r.y, sl.y, first, o.la_alpha);
+      r.z = la_sync(r.z, sl.z, first, o.la_alpha); r.w = la_sync(r.w, sl.w, first, o.la_alpha);
+      reinterpret_cast<float4*>(slow)[q] = sl;
+    }
+    reinterpret_cast<float4*>(p)[q] = r;
+    if (p_hi) {
+      const float ov[4] = {r.x, r.y, r.z, r.w};
+      union { __bf16 b[4]; uint2 u; } hh, ll;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        hh.b[j] = (__bf16)ov[j];
+        ll.b[j] = (__bf16)(ov[j] - (float)hh.b[j]);
+      }
+      reinterpret_cast<uint2*>(p_hi)[q] = hh.u;
+      reinterpret_cast<uint2*>(p_lo)[q] = ll.u;
+    }
+  }
+  if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {      // scalar tail
+    const int64_t i = (n4 << 2) + threadIdx.x;
+    const float w = p[i];
+    float mi = s1[i], vi = s2[i];
+    float wn = opt_elem<KIND>(w, grad[i], mi, vi, wd ? wd[i] : 0.f, k);
+    if (o.clear_grad) grad[i] = 0.f;
+    asum += fabsf(w);
+    s1[i] = mi; s2[i] = vi;
+    if (LA && sync) {
+      float sl = first ? wn : slow[i];
+      wn = la_sync(wn, sl, first, o.la_alpha);
+      slow[i] = sl;
+    }
+    p[i] = wn;
+    if (p_hi) {
+      const __bf16 h = (__bf16)wn;
+      const __bf16 l = (__bf16)(wn - (float)h);
+      p_hi[i] = *reinterpret_cast<const unsigned short*>(&h);
+      p_lo[i] = *reinterpret_cast<const unsigned short*>(&l);
+    }
+  }
+  if (o.abs_partial) {
+    asum = wave_sum(asum);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = asum;
+    __syncthreads();
+    if (threadIdx.x == 0) o.abs_partial[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+  }
+}
+
+template <int KIND>
+static void optim_launch(const advmil_optim_t& a, int blocks, hipStream_t stream) {
+  if (a.lookahead) hipLaunchKernelGGL((optim_kernel<KIND, true>), dim3(blocks), dim3(256), 0, stream, a);
+  else hipLaunchKernelGGL((optim_kernel<KIND, false>), dim3(blocks), dim3(256), 0, stream, a);
+}
+extern "C" int advmil_optim_step(const advmil_optim_t* a_, advmil_stream_t stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  if (!a_) return ADVMIL_EINVAL;
+  const advmil_optim_t& a = *a_;
+  if (!a.p || !a.grad || !a.s1 || !a.s2 || !a.step || a.n <= 0 || ((a.p_hi != nullptr) != (a.p_lo != nullptr))) return ADVMIL_EINVAL;
+  if (a.kind < ADVMIL_OPT_ADAM || a.kind > ADVMIL_OPT_ADADELTA) return ADVMIL_EINVAL;
+  if ((((uintptr_t)a.p | (uintptr_t)a.grad | (uintptr_t)a.s1 | (uintptr_t)a.s2 | (uintptr_t)a.wd | (uintptr_t)a.slow) & 15) ||
+      (((uintptr_t)a.p_hi | (uintptr_t)a.p_lo) & 7) || ((uintptr_t)a.m_sched & 7) || (((uintptr_t)a.step | (uintptr_t)a.la_state) & 3))
+    return ADVMIL_EINVAL;
+  // (Adadelta's rho travels as beta1; its beta2 is unused)
+  if (!(a.lr >= 0.0) || !(a.beta1 >= 0.0 && a.beta1 < 1.0) || !(a.eps >= 0.0)) return ADVMIL_EINVAL;
+  if (a.kind != ADVMIL_OPT_ADADELTA && !(a.beta2 > 0.0 && a.beta2 < 1.0 && a.beta1 > 0.0)) return ADVMIL_EINVAL;
+  if (a.kind == ADVMIL_OPT_NADAM && !a.m_sched) return ADVMIL_EINVAL;
+  if (a.lookahead && (!a.slow || !a.la_state || a.la_k < 1 || !(a.la_alpha >= 0.f && a.la_alpha <= 1.f))) return ADVMIL_EINVAL;
+  const int blocks = advmil_adam_blocks(a.n);
+  switch (a.kind) {
+    case ADVMIL_OPT_ADAM: optim_launch<ADVMIL_OPT_ADAM>(a, blocks, stream); break;
+    case ADVMIL_OPT_ADAMW: optim_launch<ADVMIL_OPT_ADAMW>(a, blocks, stream); break;
+    case ADVMIL_OPT_NADAM: optim_launch<ADVMIL_OPT_NADAM>(a, blocks, stream); break;
+    case ADVMIL_OPT_RADAM: optim_launch<ADVMIL_OPT_RADAM>(a, blocks, stream); break;
+    default: optim_launch<ADVMIL_OPT_ADADELTA>(a, blocks, stream); break;
+  }
+  if (a.tick) hipLaunchKernelGGL(step_inc_kernel, dim3(1), dim3(1), 0, stream, a.step);
+  ADVMIL_LAUNCH_CHECK();
+  return ADVMIL_OK;
+}
+
 #define ABS_BLOCKS 256
 __global__ __launch_bounds__(256) void abs_sum_partial_kernel(const float* __restrict__ p, int64_t n, float* __restrict__ partial) {
   __shared__ float red[4];

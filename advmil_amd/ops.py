@@ -991,6 +991,49 @@ def adam_step(p, grad, m, v, wd, step, lr, beta1=0.9, beta2=0.999, eps=1e-8, gra
                "adam_step")
 
 
+class OptimCall:
+    """advmil_optim_step over one set of arenas: the tensors are checked and the argument struct is filled ONCE (an optimizer's arenas
+    never move), a step only rewrites the scalars. `kind` in _lib.OPT_KINDS; s1, s2: the two state arenas (Adadelta's rho travels as
+    beta1). m_sched: NAdam's two device doubles. slow + la_state (two device int32: the step of the buffer-creating sync, the offset of
+    the lookahead step behind `step`): the lookahead wrapper, synced in the same launch."""
+
+    def __init__(self, kind, p, grad, s1, s2, wd, step, planes=None, m_sched=None, slow=None, la_state=None):
+        for nm, t in (("p", p), ("grad", grad), ("s1", s1), ("s2", s2), ("wd", wd), ("slow", slow)):
+            if t is not None and (t.dtype != torch.float32 or t.numel() != p.numel() or not t.is_contiguous()):
+                raise ValueError(f"optim_step: {nm} must be a contiguous fp32 arena of p's size")
+        if m_sched is not None and (m_sched.dtype != torch.float64 or m_sched.numel() < 2):
+            raise ValueError("optim_step: m_sched holds two float64")
+        if la_state is not None and (la_state.dtype != torch.int32 or la_state.numel() < 2):
+            raise ValueError("optim_step: la_state holds two int32")
+        self.keep = (p, grad, s1, s2, wd, step, planes, m_sched, slow, la_state)
+        self.blocks, self.wd = adam_blocks(p.numel()), _p(wd)
+        a = self.a = _lib.Optim()
+        a.kind, a.lookahead, a.n = _lib.OPT_KINDS[kind], 0 if slow is None else 1, p.numel()
+        a.p, a.grad, a.s1, a.s2, a.wd, a.slow = _p(p), _p(grad), _p(s1), _p(s2), self.wd, _p(slow)
+        a.step, a.la_state, a.m_sched = _p(step), _p(la_state), _p(m_sched)
+        a.p_hi, a.p_lo = _p(None if planes is None else planes.hi), _p(None if planes is None else planes.lo)
+        self.ref = ctypes.byref(a)
+
+    def __call__(self, lr, beta1=0.9, beta2=0.999, eps=1e-8, grad_scale=1.0, l1_coef=0.0, tick=True, abs_partial=None, clear_grad=False,
+                 schedule_decay=4e-3, la_alpha=0.5, la_k=6, use_wd=True):
+        if abs_partial is not None and (abs_partial.numel() < self.blocks or abs_partial.dtype != torch.float32):
+            raise ValueError("optim_step: abs_partial needs adam_blocks(n) fp32 entries")
+        a = self.a
+        a.lr, a.beta1, a.beta2, a.eps, a.schedule_decay = lr, beta1, beta2, eps, schedule_decay
+        a.grad_scale, a.l1_coef, a.la_alpha, a.la_k, a.tick = grad_scale, l1_coef, la_alpha, la_k, 1 if tick else 0
+        a.wd = self.wd if use_wd else None
+        a.abs_partial, a.clear_grad = _p(abs_partial), 1 if clear_grad else 0
+        _lib.check(_lib.lib().advmil_optim_step(self.ref, _stream()), "optim_step")
+
+
+def optim_step(kind, p, grad, s1, s2, wd, step, lr, beta1=0.9, beta2=0.999, eps=1e-8, grad_scale=1.0, l1_coef=0.0, planes=None, tick=True,
+               abs_partial=None, clear_grad=False, schedule_decay=4e-3, m_sched=None, slow=None, la_state=None, la_alpha=0.5, la_k=6):
+    """One advmil_optim_step launch (OptimCall built and used once; adam_step's argument order)."""
+    OptimCall(kind, p, grad, s1, s2, wd, step, planes=planes, m_sched=m_sched, slow=slow, la_state=la_state)(
+        lr, beta1, beta2, eps, grad_scale, l1_coef, tick=tick, abs_partial=abs_partial, clear_grad=clear_grad,
+        schedule_decay=schedule_decay, la_alpha=la_alpha, la_k=la_k)
+
+
 def step_seed_tick(step, seed, inc=1, step2=None):
     """step[0] += 1, step2[0] += 1 and seed[0] += inc in one launch (any may be None)."""
     _lib.check(_lib.lib().advmil_step_seed_tick(_p(step), _p(step2), _p(seed), int(inc), _stream()), "step_seed_tick")

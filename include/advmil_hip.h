@@ -394,6 +394,49 @@ int advmil_step_seed_tick(int32_t* step, int32_t* step2, uint64_t* seed, uint64_
 int advmil_abs_sum(const float* p, int64_t n, float* out, void* ws, size_t ws_bytes, advmil_stream_t stream);
 size_t advmil_abs_sum_workspace_bytes(int64_t n);
 
+/* The other elementwise optimizers a handler can reach through create_optimizer (optim/optim_factory.py:76-89, optionally behind
+ * optim/lookahead.py), one launch over the same arenas with the same options as advmil_adam_step (wd may be NULL, planes both or
+ * neither, abs_partial of advmil_adam_blocks(n) floats, clear_grad, tick). g = grad*grad_scale + l1_coef*sign(p) first; then, t = step[0] + 1:
+ *   ADAM     g += wd*p; Adam(s1 = m, s2 = v)                                        (torch.optim.Adam: the lookahead_adam base)
+ *   ADAMW    p *= 1 - lr*wd; Adam moments of g; same step                           (torch.optim.AdamW)
+ *   NADAM    g += wd*p; moments; mu_t = b1 (1 - 0.5 * 0.96^(t sd)); p -= lr (1-mu_t)/(1-M_t) g/den + lr mu_t+1/(1-M_t mu_t+1) m/den,
+ *            den = sqrt(v/(1-b2^t)) + eps, M_t = prod mu_i                          (optim/nadam.py)
+ *   RADAM    moments of g; p -= wd*lr*p; N = Nmax - 2t b2^t/(1-b2^t); N >= 5: rectified step over sqrt(v)+eps, else p -= lr/(1-b1^t) m
+ *                                                                                   (optim/radam.py::RAdam)
+ *   ADADELTA g += wd*p; s1 = square_avg, s2 = acc_delta, rho = beta1                (torch.optim.Adadelta)
+ * The step-dependent scalars (b^t, N, the rectified step size, mu_t, M_t) are evaluated in double precision on the device from
+ * `step`, so a captured launch replays; the elementwise arithmetic is fp32. NADAM keeps its running product M in m_sched[2] (device
+ * doubles): the launch of step t reads m_sched[(t-1) & 1] and leaves M_t in m_sched[t & 1].
+ * lookahead != 0 (optim/lookahead.py): lt = t - la_state[1] counts the wrapper's steps; when lt % la_k == 0 the slow arena is synced
+ * in the same launch: lt <= la_state[0] (the sync that creates the slow buffer) slow = p; later slow += la_alpha (p - slow), p = slow.
+ * The planes receive the post-sync weights. la_state: two device int32. */
+enum { ADVMIL_OPT_ADAM = 0, ADVMIL_OPT_ADAMW = 1, ADVMIL_OPT_NADAM = 2, ADVMIL_OPT_RADAM = 3, ADVMIL_OPT_ADADELTA = 4 };
+typedef struct {
+  int32_t kind;                 /* ADVMIL_OPT_* */
+  int32_t lookahead;
+  int64_t n;
+  float* p;
+  float* grad;
+  float* s1;
+  float* s2;
+  const float* wd;              /* per-element weight decay, or NULL */
+  float* slow;                  /* lookahead: the slow arena (n floats) */
+  double lr, beta1, beta2, eps; /* double: they enter the step-dependent scalars (ADADELTA: beta1 = rho) */
+  double schedule_decay;        /* NADAM */
+  float grad_scale, l1_coef;
+  float la_alpha;
+  int32_t la_k;
+  int32_t tick;
+  int32_t* step;
+  const int32_t* la_state;      /* lookahead: {first sync step, step offset} */
+  double* m_sched;              /* NADAM: two doubles */
+  void* p_hi;
+  void* p_lo;
+  float* abs_partial;
+  int32_t clear_grad;
+} advmil_optim_t;
+int advmil_optim_step(const advmil_optim_t* a, advmil_stream_t stream);
+
 /* Bag ingest from the device-resident bag cache (replaces the per-bag, per-epoch `.cuda()` of model/model_handler.py:315 for a bag
  * that has been seen before): one launch copies rows_bytes of fp32 rows and, when the four plane pointers are given, plane_bytes of
  * each bf16 operand plane, device to device, into the step slab. All pointers and sizes multiples of 16 bytes; planes all or none.
