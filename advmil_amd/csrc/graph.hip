@@ -283,6 +283,9 @@ __device__ __forceinline__ void fwd_step(const FwdRows& b, const Chunk& c, int64
   else if (pos) { if (c.n > 0) fwd_math<false, true>(b, c.n, c.first, eps, tl, st); }
   else if (c.n > 0) fwd_math<false, false>(b, c.n, c.first, eps, tl, st);
   if (c.last) {
+    // out = round(round(a1 / den) + x) in BOTH instantiations: left to the compiler, SAVE = false (agg not stored) contracted the two into
+    // one fma and the no-grad forward differed from the training forward in the last bit (tests/test_genconv_gpu.py)
+#pragma clang fp contract(off)
     const bool has = c.n > 0 || !c.first;
     float o[4], ls[4], ag[4];
 #pragma unroll

@@ -25,6 +25,7 @@ from advmil_amd import synth
 from tests import helpers as H
 from tests import poison as P
 from tests import test_attention_gpu as TA
+from tests import test_genconv_gpu as TG
 from tests import test_kernels_gpu as TK
 from tests.test_kernels_gpu import relerr, rnd
 
@@ -787,6 +788,26 @@ def test_genconv(ops, C):
         return out, xd.grad, td.grad
     runs(fn)
     under_ff(TK.test_genconv_on_random_graph_and_without_edges, C)
+
+
+@pytest.mark.parametrize("C", [128, 96])
+@pytest.mark.parametrize("name", ["ladder_s2", "unstaged_forward", "unstaged_backward"])
+def test_genconv_walks(ops, name, C):
+    """The launches of tests/test_genconv_gpu.py where launched work exceeds real work: the S = 2 degree ladder with its 5-node last
+    tile (tiles past N, half-waves past the tile's nodes, dt partials of empty workgroups) and the tiles of more than 2048 edges in the
+    forward's and in the backward's CSR image (the clamped LDS read of an unstaged tile); C = 96 walks the same graphs a wave per node."""
+    ei, N = TG.named_graph(name)                                 # (asserts on the host that the graph is where its name says)
+    x, go = TG.inputs(N, C, seed=C)
+    eid, x, go = dev(ei, x, go)
+    t = torch.tensor([1.7], device=DEV)
+
+    def fn():
+        xd, td = x.clone().requires_grad_(True), t.clone().requires_grad_(True)
+        out = ops.genconv_aggregate(xd, td, ops.GraphCSR(eid, N))
+        (out * go).sum().backward()
+        return out, xd.grad, td.grad
+    runs(fn)
+    under_ff(TG.named_case, name, C)
 
 
 def test_adam_with_a_scalar_tail(ops):
