@@ -180,6 +180,9 @@ SIGNATURES = {
     "advmil_gan_d_loss": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_float, c_float, c_void_p, c_void_p, c_void_p, c_void_p]),
     "advmil_gan_g_loss": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_float, c_float, c_int, c_float, c_float,
                                   c_float, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "advmil_gan_g_loss_disc": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_float, c_float, c_float, c_float,
+                                       c_float, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "advmil_mask_rows": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p]),
     "advmil_dx_chain_fwd": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                     c_void_p, c_void_p, c_void_p, c_float, c_float, c_void_p, c_uint64, c_uint64, c_uint64, c_void_p, c_void_p,
                                     c_void_p, c_void_p, c_void_p, c_void_p]),

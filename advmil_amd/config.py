@@ -6,6 +6,7 @@ BASELINE.json configs 1-3; 'patch' selects ESAT (config 4), 'cluster' DeepAttMIS
 def default_cfg(**over):
     cfg = dict(
         task="cont_gansurv", seed=42, cuda_id=0, save_path=None, test=False,
+        time_format="ratio", time_bins=4, log_plot=False,      # (read by task="disc_gansurv": time_format "quantile", gen_dims "384-4", disc_nety_in_dim 4)
         bcb_mode="abmil", bcb_dims="1024-384-384",
         gen_dims="384-1", gen_noi_noise="0-1", gen_noi_noise_dist="uniform", gen_noi_hops=1, gen_norm=False,
         gen_dropout=0.6, gen_out_scale="sigmoid",

@@ -13,6 +13,9 @@ What is deliberately different from the reference's schedule (results identical,
   * no per-bag host syncs: event flags come from the host copy of the labels, logs stay on the device until the
     epoch ends; the bag is never copied by a boolean mask; no empty_cache() per step;
   * the L1 term's gradient is applied inside the fused Adam kernel; its value is still added to Loss_G_total.
+Both tasks of the reference handler: cont_gansurv (the shipped config) and disc_gansurv (hazards over cfg['time_bins'] bins; the branches of
+model_handler.py:97-98, 125-130, 380-384, 399, 444-445, 460: masked label rows built by `_plan`, ops.mask_rows, ops.gan_g_loss_disc; eager
+steps, one process).
 Dataset / evaluator / wandb orchestration (exec, _run_training, _eval_all, exec_semi_sl) is out of scope
 (SURVEY.md §2 #6, #9-11): see INTEGRATION.md for how the reference's own handler binds to this class.
 """
@@ -36,11 +39,33 @@ from .model_utils import init_weights
 
 def _check_configs(cfg):
     """The constraints of model_handler.py:780-812 that concern the step."""
-    assert cfg["task"] in ("cont_gansurv",), "HIP path covers task=cont_gansurv (the only task in the shipped config)"
+    assert cfg["task"] in ("cont_gansurv", "disc_gansurv"), "HIP path covers task=cont_gansurv (the only task in the shipped config)"
     assert cfg["batch_size"] == 1, "batch_size must be 1 (one WSI per forward)"
     assert cfg["loss_netD"] in ("bce", "hinge", "wasserstein")
     assert cfg["disc_type"] in ("prj", "cat")
     assert cfg["gen_out_scale"] in ("sigmoid", "exp", "none", None)
+    if cfg["task"] == "disc_gansurv":                  # model_handler.py:786, 806-810
+        assert cfg.get("time_format") == "quantile", "task=disc_gansurv needs time_format: quantile (bin-index labels)"
+        assert cfg["gen_out_scale"] == "sigmoid", "task=disc_gansurv needs gen_out_scale: sigmoid (hazards)"
+        assert cfg["disc_nety_in_dim"] == cfg.get("time_bins"), "task=disc_gansurv needs disc_nety_in_dim == time_bins"
+        assert cfg["disc_nety_in_dim"] == int(str(cfg["gen_dims"]).split("-")[-1]), "disc_nety_in_dim must equal the last entry of gen_dims"
+        assert cfg.get("log_plot", False) == False, "task=disc_gansurv needs log_plot: False"      # noqa: E712 (the reference's comparison)
+
+
+def disc_label_rows(y, bins):
+    """Host form of the discrete task's label rows (utils/func.py:59-64 as model_handler.py:382-383, 399 call it -- the argument named
+    `c` there receives the EVENT indicator): y[n, 2] = (bin index t, e) -> (label * mask [n, bins], mask [n, bins]) as float32, with
+    z = 0..bins-1, label = (z > t) if e else (z == t), mask = (z <= t). So a real pair's row is all zeros for an event bag and one-hot at t
+    for a censored one. A bin index that is not an integer in [0, bins) raises ValueError (the loss kernel gathers at t and t + 1)."""
+    import numpy as np
+    y = np.asarray(y, dtype=np.float64).reshape(-1, 2)
+    t, e = y[:, 0:1], y[:, 1:2]
+    if not (np.all(np.isfinite(t)) and np.all(t == np.floor(t)) and np.all(t >= 0) and np.all(t < bins)):
+        raise ValueError(f"task=disc_gansurv: every label's time must be an integer bin index in [0, {bins}), got {t.reshape(-1).tolist()}")
+    z = np.arange(bins, dtype=np.float64).reshape(1, -1)
+    label = np.where(e != 0, z > t, z == t)
+    mask = z <= t
+    return (label & mask).astype(np.float32), mask.astype(np.float32)
 
 
 class LazyLog:
@@ -199,6 +224,13 @@ class MyHandler(object):
         self.cfg = cfg
         self.bcb = cfg["bcb_mode"]
         self.task = cfg["task"]
+        self.disc_task = self.task == "disc_gansurv"
+        if self.disc_task:
+            self.nbins = int(cfg["time_bins"])
+            if not 1 <= self.nbins <= ops.GAN_DISC_MAX_BINS:
+                raise ValueError(f"task=disc_gansurv: time_bins = {self.nbins}; the HIP step takes 1 to {ops.GAN_DISC_MAX_BINS} bins")
+            if self.dp.world > 1:
+                raise NotImplementedError("task=disc_gansurv is not built for bag-parallel training (world size > 1)")
 
         save_path = cfg.get("save_path")
         if save_path:
@@ -239,8 +271,16 @@ class MyHandler(object):
         # ---- losses / optimizers (model_handler.py:94-109)
         self.which_loss = cfg["loss_netD"]
         self.real_fake_loss = partial(real_fake_loss, which=cfg["loss_netD"])
-        self.supervised_loss = partial(recon_loss, **sparse_key(cfg, prefixes="loss_recon"))
-        self.supervised_terms = partial(recon_terms, **sparse_key(cfg, prefixes="loss_recon"))
+        if self.disc_task:                                 # model_handler.py:97-98, 125-130
+            from ..eval.utils import prepare_evaluator
+            from ..loss.utils import SurvMLE
+            self.supervised_loss = SurvMLE(**sparse_key(cfg, prefixes="loss_mle"))
+            self.evaluator = prepare_evaluator("discrete", mle_loss=self.supervised_loss, disc_loss=self.real_fake_loss)
+            self.metrics_list = ["c_index", "loss_mle", "loss_mle_org", "loss_fake_netD", "loss_fake_netG", "avg_fake"]
+            self.ret_metrics = ["c_index", "loss_mle_org"]
+        else:
+            self.supervised_loss = partial(recon_loss, **sparse_key(cfg, prefixes="loss_recon"))
+            self.supervised_terms = partial(recon_terms, **sparse_key(cfg, prefixes="loss_recon"))
         self._recon = dict(alpha=0.0, gamma=1.0, norm="l1")
         self._recon.update(sparse_key(cfg, prefixes="loss_recon"))
         self.coef_ganloss = cfg["loss_gan_coef"]
@@ -393,7 +433,7 @@ class MyHandler(object):
                     if len(staged_pos) == len(x_col):
                         # whole 256-row tiles for the slab kernels' fast forms; with step graphs on, whole `step_graph_rows` (2048): the
                         # padded row count is part of a graph's key, so coarser steps mean fewer captures (at most 1.6 % more rows at 16 x 8192)
-                        sg_on = self.step_graphs and self.dp.world == 1 and self.bcb == "abmil" and self.slab_pad > 0
+                        sg_on = self.step_graphs and self.dp.world == 1 and self.bcb == "abmil" and self.slab_pad > 0 and not self.disc_task
                         gran = self.slab_pad
                         if sg_on:            # <= 1.6 % more rows: 256 below 32768 rows, 2048 (step_graph_rows) from 131072 rows on
                             while gran * 2 <= self.step_graph_rows and gran * 2 * 64 <= stager.rows:
@@ -417,13 +457,13 @@ class MyHandler(object):
                 replayed = False
                 gkey = cap_ = None
                 self.rng.counter = site_base
-                if staged and len(staged_pos) == len(x_col) and self.step_graphs and self.dp.world == 1 and self.bcb == "abmil":
+                if staged and len(staged_pos) == len(x_col) and self.step_graphs and self.dp.world == 1 and self.bcb == "abmil" and not self.disc_task:
                     # launch grids of the segmented kernels for the longest bag a step-graph key admits: for EVERY staged batch of this
                     # loop, graph-eligible or not, so that eager and replayed steps (and fp32 / bf16 bag storage) share one geometry
                     lens_ = [self._rows(x[0]) for x in x_col]
                     cap_ = StaticStepPlan.bag_cap(lens_, pad, sum(lens_) + pad)
                 if (staged and len(staged_pos) == len(x_col) and self.step_graphs and self.dp.world == 1 and self.bcb == "abmil"
-                        and self.noise_hook is None and num_update_gen == 1 and ys_host is not None and bpl is not None
+                        and not self.disc_task and self.noise_hook is None and num_update_gen == 1 and ys_host is not None and bpl is not None
                         and not torch.cuda.is_current_stream_capturing()):
                     n_ = len(x_col)
                     vis_ = self._vis(mode, n_, mask)
@@ -527,7 +567,7 @@ class MyHandler(object):
     # ------------------------------------------------------------------------------------------
     def _update_disc(self, i_batch, xs, ys, mode="wlabel", label_visible_mask=None, ys_host=None, noise=None, plan=None,
                      defer_apply=False):
-        """netD.train(), netG.eval(); real pairs only for event bags with a visible label, fake pairs for all.
+        """netD.train(), netG.eval(); real pairs only for event bags with a visible label (discrete task: for every bag), fake pairs for all.
         `noise`: optional per-bag injected generator noise (tests). `plan`: the step plan (`_plan`) when the caller already built
         it for this step batch. `defer_apply`: only start D's gradient exchange; the next `_update_gen` completes the D update
         (reduce wait, log, Adam) behind its backbone forward. Returns (pred_collector, fake_collector)."""
@@ -553,6 +593,11 @@ class MyHandler(object):
         if ys_host is None:
             ys_host = [y.cpu() for y in ys]             # fallback: one sync (the epoch loop passes host labels)
         is_real = [bool(float(yh[0, 1]) == 1.0) and vis[i] for i, yh in enumerate(ys_host)]
+        rows = None
+        if self.disc_task:
+            # the reference scores a real pair for EVERY bag, event or not, visible or not (model_handler.py:380-384 has no condition)
+            is_real = [True] * n
+            rows = disc_label_rows(torch.cat([yh.reshape(1, 2) for yh in ys_host], dim=0).double().numpy(), self.nbins)
         lens = [self._rows(x[0]) for x in xs]
         W, r = self.dp.world, self.dp.rank
         counts = [sum(is_real), n, sum(vis)]
@@ -565,10 +610,19 @@ class MyHandler(object):
             n_real, n_fake, n_vis = counts
             if pad:                                      # the real rows draw what they draw in the unpadded slab (parallel.rng_row_maps)
                 rng_rows, rowoff16 = self._rng_row_maps([lens], lens, n, 1, 0, [int(pad)])
-        masks = torch.empty(2 * n, dtype=torch.float32, pin_memory=True)
+        K = self.nbins if self.disc_task else 0
+        o_t2 = (2 * n + 3) // 4 * 4                     # (the label rows start on a 16-byte boundary of the one pinned buffer)
+        masks = torch.empty(o_t2 + 3 * n * K if K else 2 * n, dtype=torch.float32, pin_memory=True)
         mv = masks.numpy()
         mv[:n] = [1.0 if q else 0.0 for q in is_real]
-        mv[n:] = [1.0 if v else 0.0 for v in vis]
+        mv[n:2 * n] = [1.0 if v else 0.0 for v in vis]
+        if K:
+            # behind the two masks: the D update's stacked label rows t2 [2n, K] -- rows [0, n) are written by mask_rows inside the
+            # step, rows [n, 2n) are the real pairs' rows label * mask -- then the fake pairs' mask (z <= t) [n, K]
+            mv[2 * n:o_t2] = 0.0
+            mv[o_t2:o_t2 + n * K] = 0.0
+            mv[o_t2 + n * K:o_t2 + 2 * n * K] = rows[0].reshape(-1)
+            mv[o_t2 + 2 * n * K:] = rows[1].reshape(-1)
         masks_d = masks.to(dev, non_blocking=True)
         # `pad` zero rows behind the bags (SlabStager.pad_rows) are one more segment of the slab: a dummy bag whose pooled row is
         # dropped (`_bags`) before anything bag-level sees it
@@ -584,9 +638,13 @@ class MyHandler(object):
         # the D update's stacked label column [fake predictions | real labels]: the lower half is constant per plan, the upper half is
         # written by the generator's head itself (no concatenation launch per step)
         t2 = torch.cat([torch.zeros(n, 1, dtype=torch.float32, device=dev), y[:, 0:1].float()], dim=0) if n_real > 0 else None
-        return SimpleNamespace(vis=vis, is_real=is_real, n_real=n_real, n_fake=n_fake, n_vis=n_vis, y=y, t2=t2,
+        lab_mask = None
+        if K:
+            t2 = masks_d[o_t2:o_t2 + 2 * n * K].view(2 * n, K)
+            lab_mask = masks_d[o_t2 + 2 * n * K:].view(n, K)
+        return SimpleNamespace(vis=vis, is_real=is_real, n_real=n_real, n_fake=n_fake, n_vis=n_vis, y=y, t2=t2, lab_mask=lab_mask,
                                y_t=y[:, 0:1].contiguous(), y_e=y[:, 1:2].contiguous(),     # label columns, contiguous once per plan
-                               vis_mask=None if all(vis) else masks_d[n:], real_mask=masks_d[:n], seg=seg, seg16=seg16,
+                               vis_mask=None if all(vis) else masks_d[n:2 * n], real_mask=masks_d[:n], seg=seg, seg16=seg16,
                                rng_rows=rng_rows, token=self._plan_count, _keep=(masks, masks_d), _X=None, _X_src=None,
                                pad=int(pad), nb=n, sel2=sel2)
 
@@ -787,8 +845,10 @@ class MyHandler(object):
         ops.MEMO.begin("record", ("G", id(self.netG), getattr(self.optimizerG, "n_updates", 0), plan.token), X)
         try:
             with torch.no_grad():                                              # the reference builds, then detaches (400)
-                pred = self.netG.finish(self._gen_features(X, plan, xs), noise=self._stack_noise(noise),
-                                        pred_out=None if plan.t2 is None else plan.t2[:len(xs)])               # [B,1]
+                pred = self.netG.finish(self._gen_features(X, plan, xs), noise=self._stack_noise(noise),      # [B,1] | hazards [B,K]
+                                        pred_out=None if (plan.t2 is None or self.disc_task) else plan.t2[:len(xs)])
+                if self.disc_task:           # the fake pairs' label rows pred * (z <= t) (model_handler.py:399) -> rows [0, B) of t2
+                    ops.mask_rows(pred, plan.lab_mask, out=plan.t2[:len(xs)])
         finally:
             ops.MEMO.end()
         f_real = f2 = None
@@ -803,7 +863,7 @@ class MyHandler(object):
             eb2, im2 = self.netD.bag_features_multi(emb, plan.seg16.twice())
             eb2, im2 = self._bags(eb2, plan, True), self._bags(im2, plan, True)
             # (pred IS the upper half of plan.t2 when the head wrote it there)
-            t2 = plan.t2 if (plan.t2 is not None and pred.data_ptr() == plan.t2.data_ptr()) else torch.cat([pred, plan.y_t], dim=0)
+            t2 = plan.t2 if (plan.t2 is not None and (self.disc_task or pred.data_ptr() == plan.t2.data_ptr())) else torch.cat([pred, plan.y_t], dim=0)
             f2 = self.netD.tail(eb2, im2, t2).view(-1)
             f_fake = f2.detach()[:nb]                                           # (the loss takes f2 whole: no slice backward)
         else:
@@ -910,7 +970,8 @@ class MyHandler(object):
         for p in d_params:
             p.requires_grad_(False)
         try:
-            f_fake = self.netD.tail(eb, im, pred).view(-1)
+            # (discrete task: D scores pred * (z <= t), kept in the graph -- model_handler.py:460-461; the loss below takes pred unmasked)
+            f_fake = self.netD.tail(eb, im, ops.mask_rows(pred, plan.lab_mask) if self.disc_task else pred).view(-1)
         finally:
             for p in d_params:
                 p.requires_grad_(True)
@@ -921,8 +982,13 @@ class MyHandler(object):
         if self.dp.world > 1:
             n_vis = plan.n_vis
         rc = self._recon
-        total, st = ops.gan_g_loss(pred, f_fake, plan.y_t, plan.y_e, plan.vis_mask, rc["alpha"], rc["gamma"], rc["norm"],
-                                   self.coef_ganloss, plan.n_fake, n_vis, root=True)
+        if self.disc_task:                   # SurvMLE over the visible bags' unmasked hazards + coef * (-mean f_fake), ONE launch
+            mle = self.supervised_loss
+            total, st = ops.gan_g_loss_disc(pred, f_fake, plan.y_t, plan.y_e, plan.vis_mask, mle.alpha, mle.eps, self.coef_ganloss,
+                                            plan.n_fake, n_vis, root=True)
+        else:
+            total, st = ops.gan_g_loss(pred, f_fake, plan.y_t, plan.y_e, plan.vis_mask, rc["alpha"], rc["gamma"], rc["norm"],
+                                       self.coef_ganloss, plan.n_fake, n_vis, root=True)
         # The engine would hand a CUDA graph to its device thread; every node of ours is a short Python function that only enqueues
         # launches, so the hand-over and the GIL ping-pong cost more than they buy (host issue per eager step 2.9 -> 2.5 ms,
         # tools/probe/eager_host_profile.py). Scoped: the caller's setting comes back on exit.

@@ -2268,6 +2268,88 @@ def gan_g_loss(pred, fake, t, e, vis_mask, alpha, gamma, norm, coef, n_fake, n_v
                             1.0 / float(n_fake), (1.0 / float(n_vis)) if n_vis > 0 else 0.0, root)
 
 
+class GanGLossDiscFn(torch.autograd.Function):
+    """The discrete task's generator loss (advmil_gan_g_loss_disc): SurvMLE over the visible hazard rows + coef * (-mean fake)."""
+
+    @staticmethod
+    def forward(ctx, hz, fake, t, e, vis, alpha, eps, coef, inv_nf, inv_nv, root=False):
+        ctx.root = root
+        hz_c, fake_c = hz.contiguous(), fake.contiguous().reshape(-1)
+        B, K = hz_c.shape
+        out = torch.empty(3, dtype=torch.float32, device=hz.device)
+        gh, gf = torch.empty_like(hz_c), torch.empty_like(fake_c)
+        t_c, e_c = t.contiguous().reshape(-1), e.contiguous().reshape(-1)      # named: a temporary's block would be reused at once
+        _lib.check(_lib.lib().advmil_gan_g_loss_disc(_p(hz_c), _p(t_c), _p(e_c), _p(vis), _p(fake_c), B, K, alpha, eps, coef, inv_nf,
+                                                     inv_nv, _p(out), _p(gh), _p(gf), _stream()), "gan_g_loss_disc")
+        ctx.save_for_backward(gh, gf)
+        ctx.fshape = fake.shape
+        ctx.mark_non_differentiable(out)
+        ctx.set_materialize_grads(False)
+        return out[0], out
+
+    @staticmethod
+    def backward(ctx, go, _):
+        gh, gf = ctx.saved_tensors
+        if go is None:
+            return (None,) * 11
+        if ctx.root:
+            return (gh, gf.reshape(ctx.fshape)) + (None,) * 9
+        return (gh * go, (gf * go).reshape(ctx.fshape)) + (None,) * 9
+
+
+GAN_DISC_MAX_BAGS = GAN_DISC_MAX_BINS = 32      # advmil_gan_g_loss_disc: one lane per bag, one row of <= 32 bins per lane
+
+
+def gan_g_loss_disc(hz, fake, t, e, vis_mask, alpha, eps, coef, n_fake, n_vis, root=False):
+    """hz[B, K] UNMASKED hazards, fake[B] scores, t[B] bin indices (fp32, every one in [0, K): the caller's duty), e[B]
+    -> (total [0-dim, differentiable in hz and fake], stats[3] = {total, mle, gen}); mle = 0 when no label is visible (n_vis == 0)."""
+    _chk(hz, "hz"); _chk(fake, "fake"); _chk(t, "t"); _chk(e, "e")
+    if hz.dim() != 2 or not (1 <= hz.shape[0] <= GAN_DISC_MAX_BAGS) or not (1 <= hz.shape[1] <= GAN_DISC_MAX_BINS):
+        raise _lib.AdvmilHipError(f"gan_g_loss_disc failed: invalid argument (hazards {tuple(hz.shape)}: 1..{GAN_DISC_MAX_BAGS} bags x "
+                                  f"1..{GAN_DISC_MAX_BINS} bins)")
+    if not (fake.numel() == t.numel() == e.numel() == hz.shape[0]) or (vis_mask is not None and vis_mask.numel() != hz.shape[0]):
+        raise ValueError("gan_g_loss_disc: fake, t, e (and vis_mask) must hold one value per hazard row")
+    return GanGLossDiscFn.apply(hz, fake, t, e, vis_mask, float(alpha), float(eps), float(coef), 1.0 / float(n_fake),
+                                (1.0 / float(n_vis)) if n_vis > 0 else 0.0, root)
+
+
+class MaskRowsFn(torch.autograd.Function):
+    """out = x * mask (advmil_mask_rows); the backward is the same launch on the incoming gradient. `mask` is a constant."""
+
+    @staticmethod
+    def forward(ctx, x, mask):
+        x_c = x.contiguous()
+        out = torch.empty_like(x_c)
+        _lib.check(_lib.lib().advmil_mask_rows(_p(x_c), _p(mask), x_c.shape[0], x_c.shape[1], _p(out), _stream()), "mask_rows")
+        ctx.save_for_backward(mask)
+        return out
+
+    @staticmethod
+    def backward(ctx, go):
+        (mask,) = ctx.saved_tensors
+        go = go.contiguous()
+        gx = torch.empty_like(go)
+        _lib.check(_lib.lib().advmil_mask_rows(_p(go), _p(mask), go.shape[0], go.shape[1], _p(gx), _stream()), "mask_rows")
+        return gx, None
+
+
+def mask_rows(x, mask, out=None):
+    """x[B, K] * mask[B, K] -> [B, K] (the discrete task's fake label rows, pred * (z <= t)). `out`: a contiguous fp32 [B, K] buffer to
+    write into (no-grad callers: the D update's stacked label rows)."""
+    _chk(x, "x"); _chk(mask, "mask")
+    if x.dim() != 2 or tuple(mask.shape) != tuple(x.shape) or not mask.is_contiguous():
+        raise ValueError(f"mask_rows: x {tuple(x.shape)} and a contiguous mask of the same shape expected, got {tuple(mask.shape)}")
+    if out is not None:
+        if torch.is_grad_enabled() and x.requires_grad:
+            raise ValueError("mask_rows: `out` is for no-grad callers")
+        if tuple(out.shape) != tuple(x.shape) or out.dtype != torch.float32 or not out.is_contiguous() or out.data_ptr() == x.data_ptr():
+            raise ValueError("mask_rows: `out` must be a contiguous fp32 buffer of x's shape, distinct from x")
+        x_c = x.contiguous()
+        _lib.check(_lib.lib().advmil_mask_rows(_p(x_c), _p(mask), x_c.shape[0], x_c.shape[1], _p(out), _stream()), "mask_rows")
+        return out
+    return MaskRowsFn.apply(x, mask)
+
+
 class SkinnyLinearFn(torch.autograd.Function):
     """y = act(x W^T + b) for in_features == 1 or out_features == 1 (advmil_skinny_linear_fwd/bwd): one launch each way, weight
     and bias gradients accumulated straight into the optimizer arena when the parameters live there."""

@@ -627,6 +627,18 @@ int advmil_gan_d_loss(const float* fake, int nf, const float* real, const float*
 int advmil_gan_g_loss(const float* pred, const float* t, const float* e, const float* vis_mask, const float* fake, int n, float alpha,
                       float gamma, int l2, float coef, float inv_nf, float inv_nv, float* out3, float* g_pred, float* g_fake,
                       advmil_stream_t stream);
+/* The discrete-time task (task: disc_gansurv), csrc/gan_disc.hip. One launch, one workgroup, fixed summation order; capturable.
+ * advmil_gan_g_loss_disc: hz[B, K] hazards (dense rows), t[B] bin index carried as fp32, e[B], vis_mask[B] (0/1) or NULL = all visible,
+ *   fake[B] scores. mle = inv_nv * sum_b vis_b SurvMLE_term(hz_b, t_b, e_b) (loss/utils.py:123-133: cumprod in bin order in fp32, both
+ *   gathers, every log argument clamped at eps; a clamped argument has zero gradient), gen = -inv_nf * sum fake.
+ *   out3 = {mle + coef * gen, mle, gen}; g_hz[B, K] = d mle / d hz (the adversarial part reaches hz through the discriminator's backward);
+ *   g_fake[B] = -coef * inv_nf. inv_nv == 0: mle = 0 and g_hz = 0. 1 <= B <= 32, 1 <= K <= 32, else ADVMIL_EINVAL before any launch; every
+ *   t must lie in [0, K): the caller's duty (a device array cannot be checked here; the kernel never forms an address outside a row).
+ * advmil_mask_rows: out[B, K] = x[B, K] * mask[B, K] (dense rows, out distinct from x), B * K < 2^31. */
+int advmil_gan_g_loss_disc(const float* hz, const float* t, const float* e, const float* vis_mask, const float* fake, int B, int K,
+                           float alpha, float eps, float coef, float inv_nf, float inv_nv, float* out3, float* g_hz, float* g_fake,
+                           advmil_stream_t stream);
+int advmil_mask_rows(const float* x, const float* mask, int64_t B, int64_t K, float* out, advmil_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * Evaluator: concordance index for right-censored data, eval/cindex.py:79-143 (`_get_comparable`,
