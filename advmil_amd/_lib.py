@@ -65,6 +65,12 @@ class GHead(ctypes.Structure):
                 ("ws", c_void_p), ("ws_bytes", c_size_t)]
 
 
+class GHeadK(ctypes.Structure):
+    """advmil_gheadk_t: advmil_ghead_t with an output layer of width K"""
+    _fields_ = [("B", ctypes.c_int32), ("d0", ctypes.c_int32), ("d1", ctypes.c_int32), ("d2", ctypes.c_int32), ("K", ctypes.c_int32),
+                ("noise_mode", ctypes.c_int32), ("out_act", ctypes.c_int32), ("reserved", ctypes.c_int32)] + GHead._fields_[6:]
+
+
 class Optim(ctypes.Structure):
     """advmil_optim_t"""
     _fields_ = [("kind", ctypes.c_int32), ("lookahead", ctypes.c_int32), ("n", c_int64), ("p", c_void_p), ("grad", c_void_p),
@@ -199,6 +205,9 @@ SIGNATURES = {
     "advmil_ghead_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
     "advmil_ghead_fwd": (c_int, [ctypes.POINTER(GHead), c_void_p]),
     "advmil_ghead_bwd": (c_int, [ctypes.POINTER(GHead), c_void_p]),
+    "advmil_gheadk_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
+    "advmil_gheadk_fwd": (c_int, [ctypes.POINTER(GHeadK), c_void_p]),
+    "advmil_gheadk_bwd": (c_int, [ctypes.POINTER(GHeadK), c_void_p]),
     "advmil_defer_sums": (c_int, [c_void_p, c_int]),
     "advmil_flush_sums": (c_int, [c_void_p]),
     "advmil_pending_sums": (c_int, [c_void_p]),

@@ -56,9 +56,10 @@ class Generator(nn.Module):
 
     def _head_spec(self, feats, zero_noise, noise):
         """ops.GHeadSpec when `finish` can run as the fused launches (csrc/ghead.hip): the shipped head -- an optional backbone `rho`
-        (Linear -> ReLU -> Dropout), MLPs[0] = Linear -> ReLU -> Dropout, uniform / zero / injected noise or none, a width-1 output layer,
-        out_scale sigmoid or none -- on <= 32 bags. Decided BEFORE any call site is drawn (the layer-by-layer path draws its own); the
-        sites are then drawn in that path's order and under its tags (abmil_rho, gen_mlp0.2, noise)."""
+        (Linear -> ReLU -> Dropout), MLPs[0] = Linear -> ReLU -> Dropout, uniform / zero / injected noise or none, an output layer of 1 to 32
+        rows (one: csrc/ghead.hip; the discrete task's hazards over K bins: csrc/gheadk.hip), out_scale sigmoid or none -- on <= 32 bags.
+        Decided BEFORE any call site is drawn (the layer-by-layer path draws its own); the sites are then drawn in that path's order and
+        under its tags (abmil_rho, gen_mlp0.2, noise)."""
         if not (ops.GHEAD and feats.is_cuda and feats.dim() == 2 and feats.dtype == torch.float32 and feats.shape[0] <= 32):
             return None
         if len(self.MLPs) != 2 or list(self.noise) not in ([0, 1], [0, 0]) or self.out_scale == "exp":
@@ -73,7 +74,7 @@ class Generator(nn.Module):
         m0, m1 = self.MLPs[0], self.MLPs[1]
         if not (isinstance(m0, nn.Sequential) and len(m0) == 3 and isinstance(m0[0], nn.Linear) and isinstance(m0[1], nn.ReLU)
                 and isinstance(m0[2], nn.Dropout) and isinstance(m1, nn.Sequential) and len(m1) == 1 and isinstance(m1[0], nn.Linear)
-                and m1[0].out_features == 1):
+                and 1 <= m1[0].out_features <= ops.GHEAD_MAX_OUT):
             return None
         B, d2 = feats.shape[0], m0[0].out_features
         has_noise = self.noise[1] == 1
@@ -116,7 +117,7 @@ class Generator(nn.Module):
         return probe
 
     def finish(self, feats, zero_noise=False, noise=None, pred_out=None):
-        """feats[B, d] (stacked `features`) -> predictions [B, dim_out]. pred_out: an fp32 [B, 1] buffer the predictions are written into
+        """feats[B, d] (stacked `features`) -> predictions [B, dim_out]. pred_out: an fp32 [B, dim_out] buffer the predictions are written into
         when the fused head runs without a graph (the D update's stacked label column); the caller checks data_ptr()."""
         spec = self._head_spec(feats, zero_noise, noise)
         if spec is not None:                 # rho + head as two launches each way

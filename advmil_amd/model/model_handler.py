@@ -14,8 +14,8 @@ What is deliberately different from the reference's schedule (results identical,
     epoch ends; the bag is never copied by a boolean mask; no empty_cache() per step;
   * the L1 term's gradient is applied inside the fused Adam kernel; its value is still added to Loss_G_total.
 Both tasks of the reference handler: cont_gansurv (the shipped config) and disc_gansurv (hazards over cfg['time_bins'] bins; the branches of
-model_handler.py:97-98, 125-130, 380-384, 399, 444-445, 460: masked label rows built by `_plan`, ops.mask_rows, ops.gan_g_loss_disc; eager
-steps, one process).
+model_handler.py:97-98, 125-130, 380-384, 399, 444-445, 460: masked label rows built by `_plan`, ops.mask_rows, ops.gan_g_loss_disc, the
+generator's head fused for K <= 32 bins; eager steps, one process or bag-parallel).
 Dataset / evaluator / wandb orchestration (exec, _run_training, _eval_all, exec_semi_sl) is out of scope
 (SURVEY.md §2 #6, #9-11): see INTEGRATION.md for how the reference's own handler binds to this class.
 """
@@ -229,8 +229,6 @@ class MyHandler(object):
             self.nbins = int(cfg["time_bins"])
             if not 1 <= self.nbins <= ops.GAN_DISC_MAX_BINS:
                 raise ValueError(f"task=disc_gansurv: time_bins = {self.nbins}; the HIP step takes 1 to {ops.GAN_DISC_MAX_BINS} bins")
-            if self.dp.world > 1:
-                raise NotImplementedError("task=disc_gansurv is not built for bag-parallel training (world size > 1)")
 
         save_path = cfg.get("save_path")
         if save_path:

@@ -2575,13 +2575,15 @@ def dtail(eb, im, t, spec):
 
 
 # ---------------------------------------------------------------------------------------
-# the generator's bag-level head as two launches each way (advmil_ghead_fwd / _bwd, csrc/ghead.hip)
+# the generator's bag-level head as two launches each way (advmil_ghead_fwd / _bwd, csrc/ghead.hip; an output layer of width 2..32:
+# advmil_gheadk_fwd / _bwd, csrc/gheadk.hip)
 # ---------------------------------------------------------------------------------------
 GHEAD = os.environ.get("ADVMIL_GHEAD", "1") != "0"
+GHEAD_MAX_OUT = 32                             # advmil_gheadk_t: 1 <= K <= 32
 
 
 class GHeadSpec:
-    """Host description of one head call: rho (Wr, br, p1, sid1) or None, MLPs[0] (W0, b0, p2, sid2), the output layer (W1, b1), the noise
+    """Host description of one head call: rho (Wr, br, p1, sid1) or None, MLPs[0] (W0, b0, p2, sid2), the output layer (W1 [K, .], b1 [K]), the noise
     input (mode 0 none / 1 zeros / 2 the caller's tensor / 3 drawn in the kernel at site sid_noise), out_act (0 / 1 = sigmoid), the dropout
     seed and the bag-level row map."""
     __slots__ = ("Wr", "br", "p1", "sid1", "W0", "b0", "p2", "sid2", "W1", "b1", "noise_mode", "noise", "sid_noise", "out_act", "seed", "rr")
@@ -2595,13 +2597,14 @@ class GHeadSpec:
 
 
 def ghead_ok(x, spec):
-    """Can this head run as the fused launches? <= 32 bags, widths within the kernel's limits, every trainable parameter with an arena slot
-    (the backward ADDS its gradients in place)."""
+    """Can this head run as the fused launches? <= 32 bags, widths within the kernels' limits (an output layer of 1..32 rows: one row takes
+    advmil_ghead_*, more take advmil_gheadk_* -- no shape within these limits exceeds the slice kernels' 160 KB of LDS), every trainable
+    parameter with an arena slot (the backward ADDS its gradients in place)."""
     if not GHEAD or not x.is_cuda or x.dim() != 2 or x.dtype != torch.float32 or not (1 <= x.shape[0] <= 32):
         return False
     d0 = x.shape[1]
     W0, W1, Wr = spec.W0, spec.W1, spec.Wr
-    if W0 is None or W1 is None or W0.dim() != 2 or W1.dim() != 2 or W1.shape[0] != 1:
+    if W0 is None or W1 is None or W0.dim() != 2 or W1.dim() != 2 or not (1 <= W1.shape[0] <= GHEAD_MAX_OUT):
         return False
     d2 = W0.shape[0]
     d1 = 0 if Wr is None else Wr.shape[0]
@@ -2637,10 +2640,20 @@ def _fill_ghead(gh, x, spec, hs, h2, pred, ws, wsb):
     gh.noise = _p(spec.noise)
     gh.hs, gh.h2, gh.pred = _p(hs), _p(h2), _p(pred)
     gh.ws, gh.ws_bytes = _p(ws), wsb
+    if isinstance(gh, _lib.GHeadK):
+        gh.K = spec.W1.shape[0]
+
+
+def _ghead_entry(spec):
+    """(struct, workspace query, fwd, bwd, names) of the head's entry points: the width-1 ones, or the width-K ones for 2..32 output rows."""
+    L, K = _lib.lib(), spec.W1.shape[0]
+    if K == 1:
+        return _lib.GHead, L.advmil_ghead_workspace_bytes, L.advmil_ghead_fwd, L.advmil_ghead_bwd, "ghead"
+    return _lib.GHeadK, (lambda B, d0, d1, d2: L.advmil_gheadk_workspace_bytes(B, d0, d1, d2, K)), L.advmil_gheadk_fwd, L.advmil_gheadk_bwd, "gheadk"
 
 
 class GHeadFn(torch.autograd.Function):
-    """pred [B, 1] = out_scale(MLPs[1](cat(MLPs[0](rho(x)), noise))) (Generator.finish behind the backbone's pooling)."""
+    """pred [B, K] = out_scale(MLPs[1](cat(MLPs[0](rho(x)), noise))) (Generator.finish behind the backbone's pooling), K = W1.shape[0]."""
 
     @staticmethod
     def forward(ctx, x, spec, pred_out, *params):
@@ -2651,17 +2664,18 @@ class GHeadFn(torch.autograd.Function):
         d1 = 0 if spec.Wr is None else spec.Wr.shape[0]
         hs = torch.empty(B, d1 if d1 else d2, dtype=torch.float32, device=dev)
         h2 = torch.empty(B, d2, dtype=torch.float32, device=dev) if d1 else None
-        if pred_out is not None and (tuple(pred_out.shape) != (B, 1) or pred_out.dtype != torch.float32 or not pred_out.is_contiguous()):
+        K = spec.W1.shape[0]
+        if pred_out is not None and (tuple(pred_out.shape) != (B, K) or pred_out.dtype != torch.float32 or not pred_out.is_contiguous()):
             pred_out = None
-        pred = pred_out if pred_out is not None else torch.empty(B, 1, dtype=torch.float32, device=dev)
-        L = _lib.lib()
-        wsb = L.advmil_ghead_workspace_bytes(B, x.shape[1], d1, d2)
+        pred = pred_out if pred_out is not None else torch.empty(B, K, dtype=torch.float32, device=dev)
+        struct, ws_bytes, fwd, _, name = _ghead_entry(spec)
+        wsb = ws_bytes(B, x.shape[1], d1, d2)
         ws = _ws(wsb, dev)
-        gh = _lib.GHead()
+        gh = struct()
         _fill_ghead(gh, x, spec, hs, h2, pred, ws, wsb)
         # (gradient slots as they stand NOW: parameters frozen around this forward stay frozen in the backward)
         ctx.slots = [(_arena_grad(p) if (p is not None and ctx.needs_input_grad[3 + j]) else None) for j, p in enumerate(spec.params())]
-        _lib.check(L.advmil_ghead_fwd(ctypes.byref(gh), _stream()), "ghead_fwd")
+        _lib.check(fwd(ctypes.byref(gh), _stream()), name + "_fwd")
         ctx.spec = spec
         ctx.has_h2 = h2 is not None
         ctx.save_for_backward(x, hs, pred, *([h2] if h2 is not None else []))
@@ -2675,22 +2689,22 @@ class GHeadFn(torch.autograd.Function):
         spec, dev = ctx.spec, x.device
         dpred = dpred.contiguous()
         dx = torch.empty(x.shape[0], x.shape[1], dtype=torch.float32, device=dev) if ctx.needs_input_grad[0] else None
-        L = _lib.lib()
+        struct, ws_bytes, _, bwd, name = _ghead_entry(spec)
         d1 = 0 if spec.Wr is None else spec.Wr.shape[0]
-        wsb = L.advmil_ghead_workspace_bytes(x.shape[0], x.shape[1], d1, spec.W0.shape[0])
+        wsb = ws_bytes(x.shape[0], x.shape[1], d1, spec.W0.shape[0])
         ws = _ws(wsb, dev)
-        gh = _lib.GHead()
+        gh = struct()
         _fill_ghead(gh, x, spec, hs, h2, pred, ws, wsb)
         gh.dpred = dpred.data_ptr()
         gh.dx, gh.lddx = _p(dx), (x.shape[1] if dx is not None else 0)
         sl = ctx.slots
         gh.dWr, gh.dbr, gh.dW0, gh.db0, gh.dW1, gh.db1 = (_p(g) for g in sl)
-        _lib.check(L.advmil_ghead_bwd(ctypes.byref(gh), _stream()), "ghead_bwd")
+        _lib.check(bwd(ctypes.byref(gh), _stream()), name + "_bwd")
         return (dx, None, None) + (None,) * len(sl)
 
 
 def ghead(x, spec, pred_out=None):
-    """pred_out (no-grad calls only): write the predictions into this [B, 1] buffer instead of a fresh tensor."""
+    """pred_out (no-grad calls only): write the predictions into this contiguous fp32 [B, K] buffer instead of a fresh tensor."""
     return GHeadFn.apply(x, spec, pred_out, *spec.params())
 
 

@@ -594,6 +594,50 @@ typedef struct {
 size_t advmil_ghead_workspace_bytes(int B, int d0, int d1, int d2);
 int advmil_ghead_fwd(const advmil_ghead_t* a, advmil_stream_t stream);
 int advmil_ghead_bwd(const advmil_ghead_t* a, advmil_stream_t stream);
+/* The same head with an output layer of width K (csrc/gheadk.hip; task disc_gansurv: hazards over K = time_bins bins): MLPs[1] =
+ * Linear(2 d2 | d2, K), W1 [K, 2 d2 | d2] row-major, b1 [K], pred / dpred [B, K] contiguous, out_act applied per element, 1 <= K <= 32.
+ * Every other field, the dropout / noise sites, their element indices and the bag-level row map are those of advmil_ghead_t; the same
+ * decomposition (16-column slices of the first hidden layer, one workgroup per bag for the finish), fp32 FMA, fixed summation order, no
+ * atomics, gradients ADDED in place. Alignment: 16 bytes for x, dx, Wr, W0, hs, ws, dWr, dW0 (float4 accesses); W1, b1, pred, dpred, dW1,
+ * db1 and the bias / h2 pointers are read and written element by element. Same shape limits as advmil_ghead_t; a call whose slice kernel
+ * would need more than 160 KB of LDS returns ADVMIL_EINVAL before any launch (no shape within the limits does).
+ * ws: advmil_gheadk_workspace_bytes = slices * B * max(d0, d2, K) floats (d1 == 0: a slice's share of the output layer is [B, K]). */
+typedef struct {
+  int32_t B, d0, d1, d2;
+  int32_t K; /* width of the output layer */
+  int32_t noise_mode, out_act;
+  int32_t reserved; /* 0 */
+  const float* x;
+  int64_t ldx;
+  const float* Wr; /* [d1, d0] */
+  const float* br;
+  const float* W0; /* [d2, d1 | d0] */
+  const float* b0;
+  const float* W1; /* [K, d2 | 2 d2] */
+  const float* b1; /* [K] */
+  float p1, p2;
+  const uint64_t* seed;
+  uint64_t sid1, sid2, sid_noise;
+  const int64_t* rng_row;
+  const float* noise;
+  float* hs;
+  float* h2;
+  float* pred; /* [B, K] */
+  const float* dpred; /* [B, K] */
+  float* dx;
+  int64_t lddx;
+  float* dWr;
+  float* dbr;
+  float* dW0;
+  float* db0;
+  float* dW1; /* [K, d2 | 2 d2] */
+  float* db1; /* [K] */
+  float* ws;
+  size_t ws_bytes;
+} advmil_gheadk_t;
+size_t advmil_gheadk_workspace_bytes(int B, int d0, int d1, int d2, int K);
+int advmil_gheadk_fwd(const advmil_gheadk_t* a, advmil_stream_t stream);
+int advmil_gheadk_bwd(const advmil_gheadk_t* a, advmil_stream_t stream);
 /* The discriminator's region-level network as one launch each way (reference model/model_utils.py:188-210 EmbedXLayer: fc1 = Linear(d, d/2)
  * -> ReLU -> Dropout -> Linear(d/2, d); model/backbone_utils.py:31-56 GAPool's scorer tanh(Linear(d, d)) * sigmoid(Linear(d, d)) -> Linear(d, 1))
  * over the R region rows of a step slab, d = 128 (the shipped disc_netx_out_dim; other widths keep the layer-by-layer path):
