@@ -1188,6 +1188,15 @@ extern "C" int advmil_colsum(const float* x, int64_t M, int64_t N, float* out, i
     else hipLaunchKernelGGL((kernel<8>), grid, dim3(256), 0, stream, __VA_ARGS__);                        \
   } while (0)
 
+// The rounded mean mu0 of a row leaves dm = mean(row - mu0) behind: round-off of a sum of d values of the row's magnitude, up to an ulp of
+// |mu0| (6e-5 for rows near 1e3), by which every normalised value of the row would be shifted, times rstd. The once-centred row is small, so
+// dm itself is exact to ITS round-off. Where that shift exceeds 2^-20 the row is centred by dm too (variance: mean c^2 - dm^2, the identity
+// for c = row - mu0); below it dm counts as 0 and every expression that takes it (c - dm, ve - dm * dm, mu0 + dm) is the uncorrected one
+// bit for bit -- rows whose mean is small against their spread, the shipped activations among them, keep their bits.
+__device__ __forceinline__ float ln_recentre(float dm, float ve /* variance + eps of the once-centred row */) {
+  return fabsf(dm) * hw_rsq(ve) > 0x1p-20f ? dm : 0.f;
+}
+
 template <int QT>
 __global__ __launch_bounds__(256) void ln_relu_mean16_fwd_kernel(const float* __restrict__ y, const float* __restrict__ gamma,
                                                                  const float* __restrict__ beta, float eps, int64_t N,
@@ -1226,19 +1235,22 @@ __global__ __launch_bounds__(256) void ln_relu_mean16_fwd_kernel(const float* __
     float s = 0.f;
 #pragma unroll
     for (int q = 0; q < QT; ++q) s += v[q];
-    const float mu = wave_sum(s) * invd;
-    float s2 = 0.f;
+    const float mu0 = wave_sum(s) * invd;
+    float s1 = 0.f, s2 = 0.f;
 #pragma unroll
     for (int q = 0; q < QT; ++q) {
       const int64_t j = lane + 64 * q;
-      const float c = (q < Q && j < d) ? v[q] - mu : 0.f;
-      s2 += c * c;
+      v[q] = (q < Q && j < d) ? v[q] - mu0 : 0.f;
+      s1 += v[q];
+      s2 += v[q] * v[q];
     }
-    const float rs = hw_rsq(wave_sum(s2) * invd + eps);
-    if (lane == 0) { mean[n] = mu; rstd[n] = rs; }
+    const float ve = wave_sum(s2) * invd + eps;
+    const float dm = ln_recentre(wave_sum(s1) * invd, ve);
+    const float rs = hw_rsq(ve - dm * dm);
+    if (lane == 0) { mean[n] = mu0 + dm; rstd[n] = rs; }
 #pragma unroll
     for (int q = 0; q < QT; ++q) {
-      const float z = (v[q] - mu) * rs * gm[q] + bt[q];
+      const float z = (v[q] - dm) * rs * gm[q] + bt[q];
       const float zr = z > 0.f ? z : 0.f;
       acc[q] += zr;
       const int64_t j = lane + 64 * q;
@@ -1294,25 +1306,34 @@ __global__ __launch_bounds__(256) void ln_relu_mean16_fwd4_kernel(const float* _
   const float invd = 1.0f / (float)d;
 #pragma unroll
   for (int it = 0; it < 2; ++it) {
+    // Every fused multiply-add of this body is written out and the optimiser forms none of its own: which products it fused moved with
+    // unrelated edits (NV = 3, whose 1 / 384 is no power of two), and the bits of the shipped widths are pinned by tests. The forms are
+    // the ones the kernel has always computed: a = x - S / d with the product unrounded, a_even^2 + (a_odd^2), gamma * (a * rstd) + beta.
+#pragma clang fp contract(off)
     const int64_t n = g * 16 + w * 4 + 2 * it + h;
     float s = 0.f;
 #pragma unroll
     for (int c = 0; c < NV; ++c) s += (va[it][c].x + va[it][c].y) + (va[it][c].z + va[it][c].w);
-    const float mu = half_sum(s) * invd;
-    float s2 = 0.f;
+    const float S = half_sum(s);
+    float s1 = 0.f, s2 = 0.f;
 #pragma unroll
     for (int c = 0; c < NV; ++c) {
-      const float a0 = va[it][c].x - mu, a1 = va[it][c].y - mu, a2 = va[it][c].z - mu, a3 = va[it][c].w - mu;
-      s2 += (a0 * a0 + a1 * a1) + (a2 * a2 + a3 * a3);
+      const float a0 = __builtin_fmaf(-invd, S, va[it][c].x), a1 = __builtin_fmaf(-invd, S, va[it][c].y);
+      const float a2 = __builtin_fmaf(-invd, S, va[it][c].z), a3 = __builtin_fmaf(-invd, S, va[it][c].w);
+      s2 += __builtin_fmaf(a0, a0, a1 * a1) + __builtin_fmaf(a2, a2, a3 * a3);
+      s1 += (a0 + a1) + (a2 + a3);
+      va[it][c] = make_float4(a0, a1, a2, a3);
     }
-    const float rs = hw_rsq(half_sum(s2) * invd + eps);
-    if (l == 0) { mean[n] = mu; rstd[n] = rs; }
+    const float ve = __builtin_fmaf(half_sum(s2), invd, eps);
+    const float dm = ln_recentre(half_sum(s1) * invd, ve);          // (see the 4-byte form)
+    const float rs = hw_rsq(ve - dm * dm);
+    if (l == 0) { mean[n] = S * invd + dm; rstd[n] = rs; }
 #pragma unroll
     for (int c = 0; c < NV; ++c) {
-      acc[c].x += fmaxf((va[it][c].x - mu) * rs * gm[c].x + bt[c].x, 0.f);
-      acc[c].y += fmaxf((va[it][c].y - mu) * rs * gm[c].y + bt[c].y, 0.f);
-      acc[c].z += fmaxf((va[it][c].z - mu) * rs * gm[c].z + bt[c].z, 0.f);
-      acc[c].w += fmaxf((va[it][c].w - mu) * rs * gm[c].w + bt[c].w, 0.f);
+      acc[c].x += fmaxf(__builtin_fmaf(gm[c].x, rs * (va[it][c].x - dm), bt[c].x), 0.f);
+      acc[c].y += fmaxf(__builtin_fmaf(gm[c].y, rs * (va[it][c].y - dm), bt[c].y), 0.f);
+      acc[c].z += fmaxf(__builtin_fmaf(gm[c].z, rs * (va[it][c].z - dm), bt[c].z), 0.f);
+      acc[c].w += fmaxf(__builtin_fmaf(gm[c].w, rs * (va[it][c].w - dm), bt[c].w), 0.f);
     }
   }
 #pragma unroll

@@ -79,6 +79,13 @@ def test_pooling_group_checks_shapes_and_workspace(L):
     assert lib.advmil_softmax_pool_fwd(p(0), p(1), D - 4, N, D, 1, None, N, p(2), p(3), p(4), need, None) == EINVAL      # pitch < D
     assert lib.advmil_softmax_pool_fwd(p(0), p(1), D, N, D, 4, None, N, p(2), p(3), p(4), need, None) == EINVAL          # 4 bags, no offsets
     assert lib.advmil_softmax_pool_fwd(p(0), ctypes.c_void_p(A16 + 8), D, N, D, 1, None, N, p(2), p(3), p(4), need, None) == EINVAL
+    # more than 2048 blocks per segment (max_len > 1 048 576) leaves the two-launch form: the mean and the planes ride in that form only
+    Nb, Db = 1049089, 16
+    need_m = lib.advmil_softmax_pool_mean_workspace_bytes(Nb, Db, 1)
+    assert lib.advmil_softmax_pool_mean_fwd(p(0), p(1), Db, Nb, Db, 1, None, Nb, p(2), p(3), p(5), p(4), need_m, None) == EINVAL
+    need_b = lib.advmil_softmax_pool_workspace_bytes(Nb, Db, 1)
+    assert lib.advmil_softmax_pool_fwd_planes(p(0), p(1), p(5), Db, Nb, Db, 1, None, Nb, p(2), p(3), p(4), need_b, None) == EINVAL
+    assert lib.advmil_softmax_pool_mean_fwd(p(0), p(1), Db, Nb, Db, 1, None, Nb, p(2), p(3), p(5), p(4), need_m - 4, None) == EWORKSPACE   # (the size check comes first)
     assert lib.advmil_gate_score_fwd(p(0), p(1), p(2), 1.5, p(3), 1, 2, N, D, p(4), None, None) == EINVAL                # p >= 1
     assert lib.advmil_ln_relu_mean16_fwd(p(0), p(1), p(2), 1e-5, 8200, 128, p(3), p(4), p(5), None, None, 1, None, 0, None) == EINVAL   # N % 16 != 0
 

@@ -14,7 +14,9 @@ and with 0x7F (3.39e38 / 2139062143). Asserted:
       No tolerance is introduced here.
 
 A case that is not run-to-run deterministic ((a) fails), or whose result moves with the pattern, is a finding: it is named here with
-the read or the unwritten element and its fix, and stays in the suite. Found so far: none (every case passed when the module was introduced)."""
+the read or the unwritten element and its fix, and stays in the suite. Found so far: none by the poisoning (every case passed when the module was introduced, and the row-kernel walks added later did too). The
+float64 bodies those walks share with tests/test_row_walks_gpu.py found one fault of their own, named there: LayerNorm rows with a mean
+large against their spread missed the 1e-5 output bound; fixed in csrc/pool.hip (ln_recentre)."""
 import ctypes
 
 import numpy as np
@@ -27,6 +29,7 @@ from tests import poison as P
 from tests import test_attention_gpu as TA
 from tests import test_genconv_gpu as TG
 from tests import test_kernels_gpu as TK
+from tests import test_row_walks_gpu as TR
 from tests.test_kernels_gpu import relerr, rnd
 
 pytestmark = pytest.mark.gpu
@@ -549,6 +552,34 @@ def test_ln_relu_rows_and_add_dropout_layer_norm(ops):
         assert relerr(got, ref.grad) < 5e-5
     for R, dd in ((37, 128), (210, 384)):
         under_ff(TA.test_add_dropout_layer_norm_vs_float64, ops, R, dd, 0.25)
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# the walks of the row kernels that the shipped widths do not reach (tests/test_row_walks_gpu.py)
+# ------------------------------------------------------------------------------------------------------------------------------
+ROW_WALKS = [
+    # the float4 map behind the statistics pass: ragged bags under a raised max_len (blocks past every segment's end write zero rows)
+    (TR.launch_pool, TR.body_pool, TR.PoolCase(20, (513, 1, 300, 77), 0, "a", True, "stats4", 32)),
+    # the backward's scalar and float4 rows: 4100-row and 1-row bags under one grid, rows past the end inside a wave's four
+    (TR.launch_pool_bwd, TR.body_pool_bwd, TR.PoolBwdCase("scalar", 6, 2, True, True)),
+    (TR.launch_pool_bwd, TR.body_pool_bwd, TR.PoolBwdCase("float4", 260, 4, True, True)),
+    # the gate score's float4 rows with idle lanes (5 float4 per branch half) and its scalar rows
+    (TR.launch_gate_score, TR.body_gate_score, TR.GateScoreCase("float4", 20, 37, 0.25, False)),
+    (TR.launch_gate_score, TR.body_gate_score, TR.GateScoreCase("scalar", 516, 37, 0.25, False)),
+    # the generic LayerNorm at QT = 4 with one column in its last group
+    (TR.launch_ln, TR.body_ln, TR.LnCase(129, 48, "offset", True, False, 1, False, "generic", 4)),
+    # colsum straight into its destination, stored and added (no partial rows, no merge)
+    (TR.launch_colsum, TR.body_colsum, TR.ColsumCase(32, 260, False, True, "direct", 1)),
+    (TR.launch_colsum, TR.body_colsum, TR.ColsumCase(32, 260, True, True, "direct", 1)),
+]
+
+
+@pytest.mark.parametrize("launch,body,case", ROW_WALKS, ids=[f"{b.__name__}-{'-'.join(str(v) for v in c)}" for _, b, c in ROW_WALKS])
+def test_row_kernel_walks(ops, launch, body, case):
+    """Each case asserts its walk on the host (the mirrors of tests/test_row_walks_gpu.py), runs four times for the bit comparison and
+    once more through its family's float64 body while the allocations are poisoned."""
+    runs(lambda: launch(case))
+    under_ff(body, case)
 
 
 # ------------------------------------------------------------------------------------------------------------------------------
