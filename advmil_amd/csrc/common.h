@@ -13,6 +13,15 @@
     if (_e != hipSuccess) return (int)_e;          \
   } while (0)
 
+// Workgroup barrier for LDS data only: __syncthreads() also drains vmcnt, i.e. waits for the ACKs of every global store issued so far
+// (the saved activations of the layer just finished: 1-2 us each time); for kernels whose waves exchange everything through LDS.
+#define LDS_BARRIER()                                   \
+  do {                                                  \
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  \
+    __builtin_amdgcn_s_barrier();                       \
+    asm volatile("" ::: "memory");                      \
+  } while (0)
+
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 

@@ -23,15 +23,6 @@
 #define RC_ROWS 64
 #define RC_PITCH 36      // fp32 patch row pitch (32 + 4)
 
-// Workgroup barrier for LDS data only: __syncthreads() also drains vmcnt, i.e. waits for the ACKs of every global store issued so far
-// (the saved activations of the layer just finished: 1-2 us each time); everything these kernels exchange between waves is in LDS.
-#define LDS_BARRIER()                                   \
-  do {                                                  \
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  \
-    __builtin_amdgcn_s_barrier();                       \
-    asm volatile("" ::: "memory");                      \
-  } while (0)
-
 #define RC_WAVE_SYNC()                                     \
   do {                                                     \
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); \

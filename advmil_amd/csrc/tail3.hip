@@ -20,15 +20,6 @@
 #define T3_PD (T3_D + 4)       // LDS row pitch of a [32][128] image
 #define T3_PH (T3_H + 4)       // ... of a [32][64] image
 
-// Workgroup barrier for LDS data only: __syncthreads() also drains vmcnt, i.e. waits for the ACKs of every global store issued so far
-// (the saved activations of the layer just finished: 1-2 us each time); everything these kernels exchange between waves is in LDS.
-#define LDS_BARRIER()                                   \
-  do {                                                  \
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  \
-    __builtin_amdgcn_s_barrier();                       \
-    asm volatile("" ::: "memory");                      \
-  } while (0)
-
 struct Tail3Args {
   advmil_dtail_t a;
 };

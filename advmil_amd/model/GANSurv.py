@@ -57,7 +57,7 @@ class Generator(nn.Module):
     def _head_spec(self, feats, zero_noise, noise):
         """ops.GHeadSpec when `finish` can run as the fused launches (csrc/ghead.hip): the shipped head -- an optional backbone `rho`
         (Linear -> ReLU -> Dropout), MLPs[0] = Linear -> ReLU -> Dropout, uniform / zero / injected noise or none, an output layer of 1 to 32
-        rows (one: csrc/ghead.hip; the discrete task's hazards over K bins: csrc/gheadk.hip), out_scale sigmoid or none -- on <= 32 bags.
+        rows (one: the width-1 form; the discrete task's hazards over K bins: the wide form), out_scale sigmoid or none -- on <= 32 bags.
         Decided BEFORE any call site is drawn (the layer-by-layer path draws its own); the sites are then drawn in that path's order and
         under its tags (abmil_rho, gen_mlp0.2, noise)."""
         if not (ops.GHEAD and feats.is_cuda and feats.dim() == 2 and feats.dtype == torch.float32 and feats.shape[0] <= 32):

@@ -2576,7 +2576,7 @@ def dtail(eb, im, t, spec):
 
 # ---------------------------------------------------------------------------------------
 # the generator's bag-level head as two launches each way (advmil_ghead_fwd / _bwd, csrc/ghead.hip; an output layer of width 2..32:
-# advmil_gheadk_fwd / _bwd, csrc/gheadk.hip)
+# advmil_gheadk_fwd / _bwd, the same source's wide form)
 # ---------------------------------------------------------------------------------------
 GHEAD = os.environ.get("ADVMIL_GHEAD", "1") != "0"
 GHEAD_MAX_OUT = 32                             # advmil_gheadk_t: 1 <= K <= 32

@@ -594,8 +594,8 @@ typedef struct {
 size_t advmil_ghead_workspace_bytes(int B, int d0, int d1, int d2);
 int advmil_ghead_fwd(const advmil_ghead_t* a, advmil_stream_t stream);
 int advmil_ghead_bwd(const advmil_ghead_t* a, advmil_stream_t stream);
-/* The same head with an output layer of width K (csrc/gheadk.hip; task disc_gansurv: hazards over K = time_bins bins): MLPs[1] =
- * Linear(2 d2 | d2, K), W1 [K, 2 d2 | d2] row-major, b1 [K], pred / dpred [B, K] contiguous, out_act applied per element, 1 <= K <= 32.
+/* The same head with an output layer of width K (the wide form of csrc/ghead.hip; task disc_gansurv: hazards over K = time_bins bins):
+ * MLPs[1] = Linear(2 d2 | d2, K), W1 [K, 2 d2 | d2] row-major, b1 [K], pred / dpred [B, K] contiguous, out_act applied per element, 1 <= K <= 32.
  * Every other field, the dropout / noise sites, their element indices and the bag-level row map are those of advmil_ghead_t; the same
  * decomposition (16-column slices of the first hidden layer, one workgroup per bag for the finish), fp32 FMA, fixed summation order, no
  * atomics, gradients ADDED in place. Alignment: 16 bytes for x, dx, Wr, W0, hs, ws, dWr, dW0 (float4 accesses); W1, b1, pred, dpred, dW1,

@@ -1,5 +1,5 @@
-"""CPU: the width-K generator head's C ABI (advmil_gheadk_workspace_bytes / _fwd / _bwd, csrc/gheadk.hip) without a device: exported and
-bound, the argument block laid out as C lays it out, the workspace query a pure host function that grows with K where a slice's share is
+"""CPU: the width-K generator head's C ABI (advmil_gheadk_workspace_bytes / _fwd / _bwd, the wide form of csrc/ghead.hip) without a device:
+exported and bound, the argument block laid out as C lays it out, the workspace query a pure host function that grows with K where a slice's share is
 [B, K], and every argument check answered before anything is launched (the pointers below are host addresses no kernel may ever see)."""
 import ctypes
 import os

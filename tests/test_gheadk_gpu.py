@@ -1,5 +1,5 @@
-"""The generator's bag-level head with an output layer of width K (advmil_gheadk_fwd / advmil_gheadk_bwd, csrc/gheadk.hip; task disc_gansurv:
-hazards over K bins): against the float64 restatement of tests/test_ghead_gpu.py widened to [B, K] -- the kernel's own dropout masks and
+"""The generator's bag-level head with an output layer of width K (advmil_gheadk_fwd / advmil_gheadk_bwd, the wide form of csrc/ghead.hip;
+task disc_gansurv: hazards over K bins): against the float64 restatement of tests/ghead_ref.py -- the kernel's own dropout masks and
 noise regenerated on the host from the recorded sites --, against the layer-by-layer path it replaces (same call sites, same draws), and
 inside one step of the handler.
 
@@ -15,12 +15,12 @@ import torch
 
 from advmil_amd import ops, synth
 from advmil_amd.optim import FlatAdam
+from tests.ghead_ref import HEAD_KEYS, close, ref, rel_err
 from tests.poison import poison  # noqa: F401  (fixture: both poison patterns)
 from tests.test_parity_gpu import DEV
 
 pytestmark = pytest.mark.gpu
 SEED = 11
-HEAD_KEYS = ("backbone.rho", "MLPs.")
 # kind -> (backbone kind, backbone dims, width of the features `finish` takes): abmil has rho (384 -> 384 -> 192), patch has none
 # (384 -> 192: the output share is K-split), g128 is PatchGCN's widths (128 -> 64)
 KINDS = {"abmil": ("abmil", [1024, 384, 384], 384), "patch": ("patch", [1024, 384, 384], 384), "g128": ("graph", [1024, 128, 128], 128)}
@@ -67,72 +67,9 @@ def run(kind, B, K, fused, train=True, zero_noise=False, inject=False, noise=(0,
         torch.cuda.synchronize()
         grads = {k: (None if p.grad is None else p.grad.detach().clone()) for k, p in g.named_parameters()}
         return dict(pred=pred.detach(), dfeats=feats.grad, grads=grads, log=list(rng.log), g=g, feats=feats, w=w, nz=nz, kind=kind,
-                    fusable=bool(taken), out_scale=out_scale)
+                    fusable=bool(taken), out_scale=out_scale, seed=SEED)
     finally:
         ops.GHEAD, ops.ghead = old, real
-
-
-def ref(r, zero_noise=False, dtype=torch.float64):
-    """The head restated in torch on the CPU in `dtype`, with the kernel's masks and noise (exact in either dtype)."""
-    g = r["g"]
-    P = {k: v.detach().cpu().to(dtype).clone().requires_grad_(True) for k, v in g.state_dict().items()}
-    x = r["feats"].detach().cpu().to(dtype).requires_grad_(True)
-
-    def site(tag):
-        ent = [e for e in r["log"] if e[0] == tag]
-        return ent[0] if ent else None
-
-    def mask(tag):
-        e = site(tag)
-        if e is None:
-            return None
-        _, sid, shape, p = e
-        u = synth.kernel_uniform(SEED, sid, int(np.prod(shape))).reshape(shape)
-        return torch.from_numpy((u >= np.float32(p)).astype(np.float64)).to(dtype) / (1 - p)
-
-    h = x
-    if r["kind"] == "abmil":
-        h = torch.relu(h @ P["backbone.rho.0.weight"].t() + P["backbone.rho.0.bias"])
-        m = mask("abmil_rho")
-        h = h * m if m is not None else h
-    h = torch.relu(h @ P["MLPs.0.0.weight"].t() + P["MLPs.0.0.bias"])
-    m = mask("gen_mlp0.2")
-    h = h * m if m is not None else h
-    W1 = P["MLPs.1.0.weight"]
-    if W1.shape[1] == 2 * h.shape[1]:
-        if zero_noise:
-            nz = torch.zeros_like(h)
-        elif r["nz"] is not None:
-            nz = r["nz"][0].cpu().to(dtype)
-        else:
-            _, sid, shape, _ = site("noise")
-            nz = torch.from_numpy(synth.kernel_uniform(SEED, sid, int(np.prod(shape))).astype(np.float64)).reshape(h.shape).to(dtype)
-        h = torch.cat([h, nz], dim=1)
-    z = h @ W1.t() + P["MLPs.1.0.bias"]
-    pred = torch.sigmoid(z) if r["out_scale"] == "sigmoid" else z
-    (pred * r["w"].cpu().to(dtype)).sum().backward()
-    return pred.detach(), x.grad, {k: v.grad for k, v in P.items()}
-
-
-def rel_err(a, b):
-    a, b = a.detach().double().cpu().reshape(-1), b.detach().double().cpu().reshape(-1)
-    assert a.shape == b.shape, (a.shape, b.shape)
-    scale = float(b.abs().max()) + 1e-12
-    return float((a - b).abs().max()), scale
-
-
-def close(a, b, tol, what, worst=None):
-    """tests/test_ghead_gpu.py::_close: |a - b| <= tol * max|b| + 1e-7."""
-    if b is None:
-        assert a is None or float(a.abs().max()) == 0.0, what
-        return
-    assert a is not None, what
-    d, scale = rel_err(a, b)
-    bound = tol * scale + 1e-7
-    print(f"  {what}: err {d:.3e} bound {bound:.3e} ratio {d / bound:.3f}")
-    if worst is not None:
-        worst[0] = max(worst[0], d / bound)
-    assert d <= bound, (what, d, scale, tol)
 
 
 def check_vs_float64(r, zero_noise=False, wide=False):
@@ -220,6 +157,34 @@ def test_two_identical_calls_give_identical_bits(poison, kind):  # noqa: F811
         assert (a["grads"][k] is None) == (b["grads"][k] is None)
         if a["grads"][k] is not None:
             assert torch.equal(a["grads"][k], b["grads"][k]), k
+
+
+@pytest.mark.parametrize("B", [1, 3])
+@pytest.mark.parametrize("kind", ["abmil", "patch"])
+def test_a_one_row_head_through_the_wide_entry(poison, monkeypatch, kind, B):  # noqa: F811
+    """K = 1 is inside advmil_gheadk_t's limits, but ops routes one-row heads to advmil_ghead_*: here ops._ghead_entry loses that route, so
+    the wide form of the shared source runs at K = 1 -- against float64 at the project bounds, and against the same head through the width-1
+    entry at the same bounds (the two sum in different orders: no exact equality)."""
+    from advmil_amd import _lib
+    narrow = run(kind, B, 1, True)
+    taken = []
+
+    def wide_entry(spec):
+        L, K = _lib.lib(), spec.W1.shape[0]
+        taken.append(K)
+        return (_lib.GHeadK, (lambda B, d0, d1, d2: L.advmil_gheadk_workspace_bytes(B, d0, d1, d2, K)), L.advmil_gheadk_fwd,
+                L.advmil_gheadk_bwd, "gheadk")
+    monkeypatch.setattr(ops, "_ghead_entry", wide_entry)
+    r = run(kind, B, 1, True)
+    assert narrow["fusable"] and r["fusable"] and taken == [1, 1]          # (forward and backward)
+    assert r["log"] == narrow["log"] and tuple(r["pred"].shape) == (B, 1)
+    print(f"{kind} B={B} K=1 through advmil_gheadk_*")
+    check_vs_float64(r)
+    close(r["pred"], narrow["pred"], 2e-6, "pred vs width-1 entry")
+    close(r["dfeats"], narrow["dfeats"], 5e-6, "d feats vs width-1 entry")
+    for k in r["grads"]:
+        if k.startswith(HEAD_KEYS):
+            close(r["grads"][k], narrow["grads"][k], 5e-6, k + " vs width-1 entry")
 
 
 def test_pred_out_buffer_is_written_in_place_only_without_grad(poison):  # noqa: F811

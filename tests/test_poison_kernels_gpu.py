@@ -680,7 +680,7 @@ def _pick(r, keys):
 @pytest.mark.parametrize("kind", ["abmil", "patch"])
 @pytest.mark.parametrize("B", [1, 3])
 def test_generator_head(kind, B):
-    from tests import test_ghead_gpu as TG
+    from tests import ghead_ref as GR, test_ghead_gpu as TG
     raw = []
 
     def fn():
@@ -688,12 +688,12 @@ def test_generator_head(kind, B):
         return _pick(raw[-1], ("pred", "dfeats", "grads"))
     runs(fn)
     r = raw[2]                                                   # the 0xFF run against float64 (test_fused_head_vs_float64_...)
-    pred, dx, gp = TG._ref64(r, kind, False)
-    TG._close(r["pred"], pred, 2e-6, "pred")
-    TG._close(r["dfeats"], dx, 5e-6, "d feats")
+    pred, dx, gp = GR.ref(r)
+    GR.close(r["pred"], pred, 2e-6, "pred")
+    GR.close(r["dfeats"], dx, 5e-6, "d feats")
     for k, g in r["grads"].items():
-        if k.startswith(TG.HEAD_KEYS):
-            TG._close(g, gp[k], 5e-6, k)
+        if k.startswith(GR.HEAD_KEYS):
+            GR.close(g, gp[k], 5e-6, k)
 
 
 @pytest.mark.parametrize("iprd,prj", [("instance", "x"), ("bag", "x"), ("instance", "y"), ("bag", None)])
