@@ -7,6 +7,7 @@ state_dict keys; every forward over N (patches) or N/16 (regions) rows runs in t
   make_embedding_layer    model/backbone_utils.py:101-111
   make_transformer_layer  model/backbone_utils.py:113-127
   AVGPoolPatchEmbedding   model/backbone_utils.py:129-168
+  GAPoolPatchEmbedding    model/backbone_utils.py:171-202
 
 The nn.Linear / nn.Conv2d / nn.LayerNorm children are parameter holders (identical keys and init);
 forward never calls them.
@@ -120,10 +121,47 @@ class AVGPoolPatchEmbedding(nn.Module):
         return self.embed_rows(x[0]).unsqueeze(0)
 
 
+class GAPoolPatchEmbedding(nn.Module):
+    """FC (1x1 conv on 4x4 tiles == row-wise FC) -> LayerNorm -> ReLU -> gated-attention pooling (GAPool, no dropout) of each
+    consecutive 16 patches. [1, N, C] -> [1, N/16, out_dim]; N % 16 == 0."""
+
+    def __init__(self, in_dim, out_dim, scale: int = 4, dw_conv: bool = False, ksize=3):
+        super().__init__()
+        assert scale == 4, "It only supports for scale = 4"
+        assert ksize == 1 or ksize == 3, "It only supports for ksize = 1 or 3"
+        if ksize != 1 or dw_conv:
+            raise NotImplementedError("HIP embedding covers ksize=1, stride=1 (cfg disc_netx_ksize: 1; ESAT ksize 1)")
+        self.scale = scale
+        self.conv = nn.Conv2d(in_dim, out_dim, ksize, 1, padding=(ksize - 1) // 2)
+        self.norm = nn.LayerNorm(out_dim)
+        self.act = nn.ReLU(inplace=True)
+        self.pool = GAPool(out_dim, out_dim, 0.0)
+
+    def embed_rows(self, x2, dup=1):
+        """x2[N_total, C] -> [dup * N_total/16, out_dim]; rows may be a slab of bags (each bag a multiple of 16 rows, so the 16-row regions
+        never straddle two bags). dup = 2: the embedding twice, stacked, straight from the pooling kernel. The FC comes first and takes
+        its bias as it is, so a result parked by ops.prefill_two_layers is taken exactly as the avgpool layer takes it."""
+        assert x2.shape[0] % (self.scale * self.scale) == 0
+        pl = self.pool
+        y = ops.linear_act(x2, self.conv.weight, self.conv.bias, "none")
+        z = ops.ln_relu(y, self.norm.weight, self.norm.bias, self.norm.eps)
+        s = ops.gate_scores(z, pl.fc1[0].weight, pl.fc1[0].bias, pl.score[0].weight, pl.score[0].bias, pl.fc2.weight, pl.fc2.bias, p=0.0)
+        emb, A = ops.gapool16(s, z, dup)
+        self.last_attention = A.detach()
+        return emb
+
+    def forward(self, x):
+        if x.dim() != 3 or x.shape[0] != 1:
+            raise ValueError("GAPoolPatchEmbedding: batch_size 1 expected, got %s" % (tuple(x.shape),))
+        return self.embed_rows(x[0]).unsqueeze(0)
+
+
 def make_embedding_layer(backbone: str, args):
     if backbone == "avgpool":
         return AVGPoolPatchEmbedding(args.in_dim, args.out_dim, args.scale, args.dw_conv, args.ksize)
-    raise NotImplementedError(f"{backbone}: only `avgpool` is reachable from the shipped configs (cfg_nlst.yaml:42)")
+    if backbone == "gapool":
+        return GAPoolPatchEmbedding(args.in_dim, args.out_dim, args.scale, args.dw_conv, args.ksize)
+    raise NotImplementedError(f"{backbone} has not implemented.")
 
 
 def make_transformer_layer(backbone: str, args):

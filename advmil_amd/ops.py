@@ -2085,6 +2085,49 @@ def ln_relu(y, gamma, beta, eps=1e-5):
     return LNReLUFn.apply(y, gamma, beta, eps)
 
 
+class GAPool16Fn(torch.autograd.Function):
+    """Gated-attention pooling of each consecutive 16 rows (GAPoolPatchEmbedding's tail, model/backbone_utils.py:197-201):
+    s[N] raw scores, z[N,d] -> (emb[dup N/16, d], A[N]). One launch each way (csrc/gapool16.hip): the segment of a row is row >> 4, so
+    there are no offsets or row ids to build and nothing outside a StaticStepPlan to capture."""
+
+    @staticmethod
+    def forward(ctx, s, z, dup):
+        _chk(s, "s"); _chk(z, "z")
+        if z.dim() != 2 or z.stride(1) != 1 or z.stride(0) % 4 or z.stride(0) < z.shape[1] or z.data_ptr() % 16:
+            z = z.contiguous()
+        s = s.reshape(-1).contiguous()
+        N, d = z.shape
+        if s.numel() != N:
+            raise ValueError(f"gapool16: {s.numel()} scores for {N} rows")
+        A = torch.empty(N, dtype=torch.float32, device=z.device)
+        emb = torch.empty((dup * (N // 16), d), dtype=torch.float32, device=z.device)
+        _lib.check(_lib.lib().advmil_gapool16_fwd(_p(s), _p(z), z.stride(0), N, d, _p(A), _p(emb), dup, _stream()), "gapool16_fwd")
+        ctx.save_for_backward(A, z)
+        ctx.dup = dup
+        ctx.mark_non_differentiable(A)
+        return emb, A
+
+    @staticmethod
+    def backward(ctx, demb, _dA):
+        A, z = ctx.saved_tensors
+        N, d = z.shape
+        demb = demb.contiguous()
+        ds = torch.empty(N, dtype=torch.float32, device=z.device)
+        dz = torch.empty((N, d), dtype=torch.float32, device=z.device)
+        _lib.check(_lib.lib().advmil_gapool16_bwd(_p(demb), _p(A), _p(z), z.stride(0), N, d, ctx.dup, _p(ds), _p(dz), 0, _stream()),
+                   "gapool16_bwd")
+        return ds, dz, None
+
+
+def gapool16(s, z, dup=1):
+    """-> (emb [dup * N / 16, d], A [N]): softmax of s over each 16 consecutive rows, emb = the weighted row sums. dup = 2: [emb; emb]
+    from the kernel (the discriminator update's stacked fake | real batch); the backward sums the two halves of its gradient on load.
+    The gradient of z that comes back through the scores (the gate contraction's dh) and the pooling's own are added by autograd."""
+    if dup not in (1, 2):
+        raise ValueError(f"gapool16: dup = {dup}")
+    return GAPool16Fn.apply(s, z, int(dup))
+
+
 class GraphCSR:
     """Both CSR images of a WSI patch graph edge_index[2, E] (row 0 = source, row 1 = target; layout of
     tools/patchgcn_graph_s2.py:78-80). Built once per graph with integer device ops (sort / bincount / cumsum)."""

@@ -357,6 +357,23 @@ int advmil_ln_relu_bwd(const float* dout, const float* y, const float* gamma, co
                        void* ws, size_t ws_bytes, advmil_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Region embedding tail of GAPoolPatchEmbedding (model/backbone_utils.py:171-202): gated-attention pooling of each consecutive 16
+ * rows. s[N] = the rows' raw gate scores, z[N,d] (row pitch ldz) = the rows that are pooled (relu(LayerNorm(FC x))); region r is rows
+ * [16 r, 16 r + 16), R = N / 16:
+ *   A[16 r + i] = softmax_i s[16 r + i],   emb[r, :] = sum_i A[16 r + i] z[16 r + i, :]   (i ascending: the bits do not depend on the grid)
+ * dup = 2: emb has 2 R rows, the embedding written twice ([emb; emb], as advmil_ln_relu_mean16_fwd does); the backward then takes
+ * demb [2 R, d] and sums its halves on load.
+ * bwd, g = demb[r] (+ demb[R + r]): ds[16 r + i] = A_i (z_i . g - sum_j A_j z_j . g), dz[16 r + i, :] (contiguous, pitch d) = A_i g,
+ * added onto dz when dz_accumulate != 0 and written otherwise.
+ * One launch each way: no workspace, no atomics, no segment arrays, no host synchronisation (capturable).
+ * Shapes: N > 0, N % 16 == 0; 4 <= d <= 512 with d % 4 == 0 (the widths advmil_ln_relu_fwd takes, in 16-byte units); ldz >= d,
+ * ldz % 4 == 0; dup 1 | 2; z, emb, demb, dz 16-byte aligned. Anything else: ADVMIL_EINVAL before any launch. */
+int advmil_gapool16_fwd(const float* s, const float* z, int64_t ldz, int64_t N, int64_t d, float* A, float* emb, int dup,
+                        advmil_stream_t stream);
+int advmil_gapool16_bwd(const float* demb, const float* A, const float* z, int64_t ldz, int64_t N, int64_t d, int dup, float* ds,
+                        float* dz, int dz_accumulate, advmil_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * PatchGCN's GENConv softmax aggregation (model/backbone.py:139,157 -> torch_geometric.nn.GENConv, aggr='softmax',
  * learn_t; parity unpinned: restated from the published semantics). x[N,C]; the graph arrives as two int32 CSR images:
  *   by destination (rowptr_dst[N+1], col_src[E] = source of each in-edge)  -> forward
