@@ -404,6 +404,141 @@ extern "C" int advmil_stage_bag(void* dst_rows, const void* src_rows, size_t row
   return ADVMIL_OK;
 }
 
+// advmil_stage_bag with a keep bitmap over the bag's 16-row regions (the occlusion-robustness test: reference utils/func.py:14-40
+// random_mask_square_instance, way mask_zero, applied here in the launch that stages the resident CLEAN bag). Bit r & 31 of word r >> 5
+// = region r (rows [16 r, 16 r + 16)) is kept. A kept region is copied (its planes copied or derived), a masked region is WRITTEN as
+// zeros in the rows and both planes -- the slab holds the batch before -- and never read from the source.
+// Work item = one chunk of one region (2^cshift chunks per region), so the keep bit is uniform over a workgroup: one branch per item,
+// no index division. A region of 16 rows is `row bytes` 16-byte units long, whatever the row width.
+__device__ __forceinline__ bool region_kept(const uint32_t* __restrict__ keep_bits, int64_t r) {
+  return (keep_bits[r >> 5] >> (unsigned)(r & 31)) & 1u;
+}
+struct MaskSpan { uint4* dst; const uint4* src; uint32_t upr; };      // upr: 16-byte units per region (0: span absent)
+__global__ __launch_bounds__(256) void stage_bag_masked_kernel(MaskSpan a, MaskSpan b, MaskSpan c, const uint32_t* __restrict__ keep_bits,
+                                                               int64_t items, int cshift) {
+  const MaskSpan sp = blockIdx.y == 0 ? a : (blockIdx.y == 1 ? b : c);
+  const uint32_t nch = 1u << cshift, chunk = (sp.upr + nch - 1) >> cshift;
+  const uint4 zero = make_uint4(0u, 0u, 0u, 0u);
+  for (int64_t it = blockIdx.x; it < items; it += gridDim.x) {
+    const int64_t r = it >> cshift;
+    const uint32_t u0 = ((uint32_t)it & (nch - 1)) * chunk;
+    const uint32_t u1 = u0 + chunk < sp.upr ? u0 + chunk : sp.upr;
+    uint4* d = sp.dst + r * (int64_t)sp.upr;
+    const uint4* s = sp.src + r * (int64_t)sp.upr;
+    uint32_t u = u0 + threadIdx.x;
+    if (region_kept(keep_bits, r)) {
+      if (d == s) continue;                            // (in place: a kept region stays as it arrived)
+      for (; u + 768 < u1; u += 1024) {
+        const uint4 v0 = s[u], v1 = s[u + 256], v2 = s[u + 512], v3 = s[u + 768];
+        d[u] = v0; d[u + 256] = v1; d[u + 512] = v2; d[u + 768] = v3;
+      }
+      for (; u < u1; u += 256) d[u] = s[u];
+    } else {
+      for (; u < u1; u += 256) d[u] = zero;
+    }
+  }
+}
+// fp32 rows with the planes derived on the way (the rounding of stage_bag_split_kernel, statement for statement). One thread = 8
+// consecutive floats; upr8 = 32-byte units per region. dst == NULL: planes only (the source is a cache entry and is never written);
+// dst == src: rows that just arrived over PCIe -- a kept region only gets its planes, a masked one is zeroed where it lies.
+__global__ __launch_bounds__(256) void stage_bag_masked_split_kernel(const float* src, float* dst, uint32_t upr8, uint4* __restrict__ hi,
+                                                                     uint4* __restrict__ lo, const uint32_t* __restrict__ keep_bits,
+                                                                     int64_t items, int cshift) {
+  const uint32_t nch = 1u << cshift, chunk = (upr8 + nch - 1) >> cshift;
+  const bool copy = dst != nullptr && dst != src;
+  const uint4 zero = make_uint4(0u, 0u, 0u, 0u);
+  for (int64_t it = blockIdx.x; it < items; it += gridDim.x) {
+    const int64_t r = it >> cshift;
+    const uint32_t u0 = ((uint32_t)it & (nch - 1)) * chunk;
+    const uint32_t u1 = u0 + chunk < upr8 ? u0 + chunk : upr8;
+    const int64_t base = r * (int64_t)upr8;
+    if (region_kept(keep_bits, r)) {
+      for (uint32_t u = u0 + threadIdx.x; u < u1; u += 256) {
+        const int64_t idx = base + u;
+        const float4 a = reinterpret_cast<const float4*>(src)[2 * idx], b = reinterpret_cast<const float4*>(src)[2 * idx + 1];
+        if (copy) {
+          reinterpret_cast<float4*>(dst)[2 * idx] = a;
+          reinterpret_cast<float4*>(dst)[2 * idx + 1] = b;
+        }
+        const float x[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
+        union { __bf16 v[8]; uint4 u; } h, l;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          h.v[j] = (__bf16)x[j];
+          l.v[j] = (__bf16)(x[j] - (float)h.v[j]);
+        }
+        hi[idx] = h.u;
+        lo[idx] = l.u;
+      }
+    } else {
+      for (uint32_t u = u0 + threadIdx.x; u < u1; u += 256) {
+        const int64_t idx = base + u;
+        if (dst) {
+          reinterpret_cast<uint4*>(dst)[2 * idx] = zero;
+          reinterpret_cast<uint4*>(dst)[2 * idx + 1] = zero;
+        }
+        hi[idx] = zero;
+        lo[idx] = zero;
+      }
+    }
+  }
+}
+
+// chunks per region: the largest power of two that still leaves every thread of a workgroup `per_thread` units of a chunk
+static int stage_chunk_shift(uint64_t upr, uint32_t per_thread) {
+  int s = 0;
+  while (s < 8 && (upr >> (s + 1)) >= 256ull * per_thread) ++s;
+  return s;
+}
+
+extern "C" int advmil_stage_bag_masked(void* dst_rows, const void* src_rows, size_t rows_bytes, int64_t n_rows, void* dst_hi,
+                                       const void* src_hi, void* dst_lo, const void* src_lo, size_t plane_bytes,
+                                       const uint32_t* keep_bits, advmil_stream_t stream_) {
+  if (!src_rows || !keep_bits || rows_bytes == 0 || (rows_bytes & 15) || n_rows <= 0 || (n_rows & 15)) return ADVMIL_EINVAL;
+  const bool planes = dst_hi || src_hi || dst_lo || src_lo || plane_bytes;
+  const bool split = planes && !src_hi && !src_lo;                 // planes wanted, none held: derive them from the rows
+  if (planes && (!dst_hi || !dst_lo || plane_bytes == 0 || (plane_bytes & 15))) return ADVMIL_EINVAL;
+  if (planes && !split && (!src_hi || !src_lo)) return ADVMIL_EINVAL;
+  if (!dst_rows && !split) return ADVMIL_EINVAL;                   // no row copy only where the planes are derived (planes-only staging)
+  if (((uintptr_t)dst_rows | (uintptr_t)src_rows | (uintptr_t)dst_hi | (uintptr_t)src_hi | (uintptr_t)dst_lo | (uintptr_t)src_lo) & 15)
+    return ADVMIL_EINVAL;
+  if ((uintptr_t)keep_bits & 3) return ADVMIL_EINVAL;
+  const uint64_t R = (uint64_t)n_rows >> 4;                        // regions; one of them is rows_bytes / R bytes = 16 rows
+  if (rows_bytes % (size_t)n_rows) return ADVMIL_EINVAL;
+  const uint64_t row_bytes = rows_bytes / (size_t)n_rows;          // = 16-byte units per region
+  if (row_bytes > 0x7fffffffull) return ADVMIL_EINVAL;
+  static const int64_t cap = []() { const char* e = getenv("ADVMIL_STAGE_BLOCKS"); return (int64_t)(e ? atoi(e) : 192); }();
+  if (split) {
+    if (plane_bytes * 2 != rows_bytes || (row_bytes & 1)) return ADVMIL_EINVAL;         // bf16 planes of fp32 rows, 8 floats per thread
+    const uint32_t upr8 = (uint32_t)(row_bytes >> 1);
+    const int cshift = stage_chunk_shift(upr8, 2);
+    const int64_t items = (int64_t)R << cshift;
+    int64_t blocks = items < cap ? items : cap;
+    if (blocks < 1) blocks = 1;
+    hipLaunchKernelGGL(stage_bag_masked_split_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream_, (const float*)src_rows,
+                       (float*)dst_rows, upr8, (uint4*)dst_hi, (uint4*)dst_lo, keep_bits, items, cshift);
+    ADVMIL_LAUNCH_CHECK();
+    return ADVMIL_OK;
+  }
+  uint64_t plane_upr = 0;
+  if (planes) {
+    if ((plane_bytes >> 4) % R) return ADVMIL_EINVAL;              // whole 16-byte units per region in the planes as well
+    plane_upr = (plane_bytes >> 4) / R;
+    if (plane_upr > 0x7fffffffull) return ADVMIL_EINVAL;
+  }
+  MaskSpan a{(uint4*)dst_rows, (const uint4*)src_rows, (uint32_t)row_bytes};
+  MaskSpan b{(uint4*)dst_hi, (const uint4*)src_hi, (uint32_t)plane_upr};
+  MaskSpan c{(uint4*)dst_lo, (const uint4*)src_lo, (uint32_t)plane_upr};
+  const int cshift = stage_chunk_shift(row_bytes, 4);
+  const int64_t items = (int64_t)R << cshift;
+  int64_t blocks = items < cap ? items : cap;
+  if (blocks < 1) blocks = 1;
+  hipLaunchKernelGGL(stage_bag_masked_kernel, dim3((unsigned)blocks, planes ? 3 : 1), dim3(256), 0, (hipStream_t)stream_, a, b, c, keep_bits,
+                     items, cshift);
+  ADVMIL_LAUNCH_CHECK();
+  return ADVMIL_OK;
+}
+
 // rng_row (optional, with the row width `width`): element i of the flat tensor belongs to row i / width, whose draws are indexed
 // as row rng_row[i / width] -- the row it would occupy in the single-process run (bag-parallel world-size invariance)
 __device__ __forceinline__ uint64_t rng_flat_index(int64_t i, const int64_t* rng_row, int64_t width) {

@@ -12,6 +12,9 @@ The loader hands over CPU tensors `x[1, N, 1024]`. `SlabStager` owns two (pinned
     `pad_rows` appends zero rows up to whole 256-row tiles (a dummy bag the handlers drop after pooling).
   * While step t computes on set k, the host already stages step t+1 into set k^1 (PCIe / D2D overlap compute); a set is only
     rewritten after the step that read it has finished (event from the compute stream).
+  * The occlusion-robustness test (reference model_handler.py:189-224 `exec_test` with test_mask_ratio; the dataset zeroes random
+    4x4 "square instances" on the host: dataset/PatchWSI.py:80-81) keeps the CLEAN bag resident and masks on the way into the slab:
+    `step_batches(mask=...)` draws one kept-region set per bag and the staging launch applies it (`advmil_stage_bag_masked`).
 `step_batches` is the generator both handlers' loops and evaluations are built on.
 """
 import os
@@ -95,6 +98,10 @@ class SlabStager:
         self.split = False                # derive every staged bag's bf16x3 operand planes on the copy stream (set per batch by begin())
         self.hint_rows = 0                # expected rows of a step batch (first allocation of the slabs; see _ensure)
         self.max_bag_rows = 0             # longest bag staged so far (expect(): ragged cohorts start a batch with any length)
+        self.bits_host = [None, None]     # keep bitmaps of a masked batch (uint32 words as int32, pinned) and their device image: they
+        self.bits_dev = [None, None]      # belong to pair k and are protected by its events (begin(): h2d_evt, free_evt)
+        self.bits_np = [None, None]       # (numpy views of bits_host)
+        self.bits_w = 0                   # words of the current batch's bitmaps written so far
 
     def _ensure(self, k, rows):
         cap = 0 if self.dev[k] is None else self.dev[k].shape[0]
@@ -157,15 +164,50 @@ class SlabStager:
         self.views = []
         self._spans = []
         self._keep = []
-        self._stale = []                      # (a, b, cached rows): spans whose fp32 rows were NOT copied (planes-only staging)
+        self._stale = []                      # (a, b, cached rows, keep bits): spans whose fp32 rows were NOT copied (planes-only staging)
+        self.bits_w = 0
         self.stale = False
         if self.free_evt[self.k] is not None:                    # do not overwrite bags a running step still reads
             self.copy_stream.wait_event(self.free_evt[self.k])
 
-    def add(self, x_cpu):
-        """Stage one bag x[1, N, C] (CPU) -> device view [1, N, C] inside the slab (valid after `ready()`)."""
+    def _send_bits(self, keep, n):
+        """Keep bitmap of one bag of n rows -> its words in pair k's device bitmap buffer (returned as a view): written into the pinned
+        buffer and copied behind the bag on the copy stream, with no host synchronisation. A buffer that has to grow in the middle of a
+        batch is replaced, not copied: the launches already enqueued hold the old one (`_keep`)."""
+        from .utils.func import keep_bitmap
+        k = self.k
+        words = keep_bitmap(keep, n // 16)
+        w0, w1 = self.bits_w, self.bits_w + len(words)
+        if self.bits_host[k] is None or self.bits_host[k].numel() < w1:
+            cap = max(4096, 2 * w1)
+            if self.bits_host[k] is not None:
+                self._keep.append((self.bits_host[k], self.bits_dev[k]))
+            self.bits_host[k] = torch.empty(cap, dtype=torch.int32).pin_memory()
+            self.bits_np[k] = self.bits_host[k].numpy().view("uint32")       # (the same pinned words, written without a torch call)
+            with torch.cuda.stream(self.copy_stream):            # (the copy stream's own pool: written and read on this stream only)
+                self.bits_dev[k] = torch.empty(cap, dtype=torch.int32, device=self.device)
+        self.bits_np[k][w0:w1] = words
+        dev = self.bits_dev[k][w0:w1]
+        with torch.cuda.stream(self.copy_stream):
+            dev.copy_(self.bits_host[k][w0:w1], non_blocking=True)
+        self.bits_w = w1
+        return dev
+
+    def _stage_masked(self, dst_rows, src_rows, n, esz, hi, src_hi, lo, src_lo, bits, what):
+        """advmil_stage_bag_masked on the copy stream for one bag of n rows of `esz`-byte elements."""
+        from . import _lib
+        C = self.channels
+        _lib.check(_lib.lib().advmil_stage_bag_masked(dst_rows, src_rows, n * C * esz, n, hi, src_hi, lo, src_lo,
+                                                      0 if hi is None else n * C * 2, bits.data_ptr(), self.copy_stream.cuda_stream), what)
+
+    def add(self, x_cpu, keep=None, on_clean=None):
+        """Stage one bag x[1, N, C] (CPU) -> device view [1, N, C] inside the slab (valid after `ready()`). `keep` (kept region
+        indices, utils.func.square_instance_keep): the bag's other regions are zeroed where they lie in the slab, behind the copy;
+        `on_clean(view)` is called on the copy stream between the two, while the span still holds the clean bag (the bag cache's copy)."""
         x2 = x_cpu.reshape(-1, x_cpu.shape[-1])
         n = x2.shape[0]
+        if keep is not None and n % 16:
+            raise ValueError(f"a masked bag must consist of whole 16-row regions, got {n} rows")
         self.max_bag_rows = max(self.max_bag_rows, n)
         k = self.k
         self._spans.append((self.rows, self.rows + n))
@@ -187,7 +229,25 @@ class SlabStager:
             C = self.channels
             _lib.check(_lib.lib().advmil_split_planes(self.dev32[k].data_ptr() + a * C * 4, n * C, self.dev[k].data_ptr() + a * C * 2, None,
                                                       self.copy_stream.cuda_stream), "split_planes(bf16 slab)")
-        if self.split and self.planes_rows == a and self._split_ok(n):
+        if keep is not None and on_clean is not None:
+            if len(self.views) < len(self._spans):
+                self.views.append(self.dev[k][a:b].unsqueeze(0))
+            with torch.cuda.stream(self.copy_stream):
+                on_clean(self.views[-1])
+        if keep is not None:
+            # masked in place behind the copy (each thread reads an element before it writes it); with the planes when this batch splits
+            bits = self._send_bits(keep, n)
+            C, esz = self.channels, self.dev[k].element_size()
+            p0 = self.dev[k].data_ptr() + a * C * esz
+            if self.split and self.planes_rows == a and self._split_ok(n):
+                self._ensure_planes(k)
+                pl = self.pl[k]
+                self._stage_masked(p0, p0, n, esz, pl.hi.data_ptr() + a * C * 2, None, pl.lo.data_ptr() + a * C * 2, None, bits,
+                                   "stage_bag_masked(in place, planes)")
+                self.planes_rows = b
+            else:
+                self._stage_masked(p0, p0, n, esz, None, None, None, None, bits, "stage_bag_masked(in place)")
+        elif self.split and self.planes_rows == a and self._split_ok(n):
             # the bag's operand planes behind its H2D copy, on the copy stream: the step slab's planes are complete when it is
             self._ensure_planes(k)
             from . import _lib
@@ -204,12 +264,15 @@ class SlabStager:
     def _split_ok(self, n):
         return self.dtype == torch.float32 and (n * self.channels) % 8 == 0
 
-    def add_device(self, x_dev, planes=None, ready_evt=None):
+    def add_device(self, x_dev, planes=None, ready_evt=None, keep=None):
         """Stage one bag that is ALREADY in HBM (the device-resident bag cache): device-to-device copies of its fp32 rows -- and of
         its operand planes, when it carries them -- into the slab on the copy stream, i.e. under the compute of the step before.
-        `ready_evt`: event recorded on the compute stream behind the kernels that produced the cached tensors."""
+        `ready_evt`: event recorded on the compute stream behind the kernels that produced the cached tensors. `keep` (kept region
+        indices): the same launch writes the bag's other regions as zeros (advmil_stage_bag_masked); the entry is read only."""
         x2 = x_dev.reshape(-1, x_dev.shape[-1])
         n = x2.shape[0]
+        if keep is not None and n % 16:
+            raise ValueError(f"a masked bag must consist of whole 16-row regions, got {n} rows")
         self.max_bag_rows = max(self.max_bag_rows, n)
         k = self.k
         self._spans.append((self.rows, self.rows + n))
@@ -240,13 +303,24 @@ class SlabStager:
         # flagged (`stale`, -> `_advmil_fp32_stale` on the step slab, ops.gemm then takes planes only); a batch that ends up without
         # complete planes or below the handler's plane threshold gets its rows after all (`_backfill`, from `ready`).
         only = bool(derive and pl is not None and PLANES_ONLY_STAGE)
-        rc = _lib.lib().advmil_stage_bag(
-            (x2.data_ptr() if only else dst.data_ptr() + a * C * esz), x2.data_ptr(), n * C * esz,
-            None if pl is None else pl.hi.data_ptr() + a * C * 2, None if (pl is None or derive) else planes.hi.data_ptr(),
-            None if pl is None else pl.lo.data_ptr() + a * C * 2, None if (pl is None or derive) else planes.lo.data_ptr(),
-            0 if pl is None else n * C * 2, self.copy_stream.cuda_stream)
-        if rc == 0 and only:
-            self._stale.append((a, b, x2))
+        if keep is not None:
+            bits = self._send_bits(keep, n)
+            held = pl is not None and not derive
+            self._stage_masked(None if only else dst.data_ptr() + a * C * esz, x2.data_ptr(), n, esz,
+                               None if pl is None else pl.hi.data_ptr() + a * C * 2, planes.hi.data_ptr() if held else None,
+                               None if pl is None else pl.lo.data_ptr() + a * C * 2, planes.lo.data_ptr() if held else None, bits,
+                               "stage_bag_masked(cached bag)")
+            if only:
+                self._stale.append((a, b, x2, bits))
+            rc = 0
+        else:
+            rc = _lib.lib().advmil_stage_bag(
+                (x2.data_ptr() if only else dst.data_ptr() + a * C * esz), x2.data_ptr(), n * C * esz,
+                None if pl is None else pl.hi.data_ptr() + a * C * 2, None if (pl is None or derive) else planes.hi.data_ptr(),
+                None if pl is None else pl.lo.data_ptr() + a * C * 2, None if (pl is None or derive) else planes.lo.data_ptr(),
+                0 if pl is None else n * C * 2, self.copy_stream.cuda_stream)
+            if rc == 0 and only:
+                self._stale.append((a, b, x2, None))
         if rc != 0:                                   # unaligned rows (channels not a multiple of 8): the general copies
             with torch.cuda.stream(self.copy_stream):
                 dst[a:b].copy_(x2, non_blocking=True)
@@ -294,8 +368,13 @@ class SlabStager:
     def _backfill(self):
         """The fp32 rows of the spans staged as planes only, after all (this batch will be read as fp32 rows)."""
         with torch.cuda.stream(self.copy_stream):
-            for a, b, x2 in self._stale:
-                self.dev[self.k][a:b].copy_(x2, non_blocking=True)
+            for a, b, x2, bits in self._stale:
+                if bits is None:
+                    self.dev[self.k][a:b].copy_(x2, non_blocking=True)
+                else:                                 # a masked span gets its rows under the same bitmap (still in pair k's buffer)
+                    esz = x2.element_size()
+                    self._stage_masked(self.dev[self.k].data_ptr() + a * self.channels * esz, x2.data_ptr(), b - a, esz, None, None, None,
+                                       None, bits, "stage_bag_masked(backfill)")
         self._stale = []
 
     def ready(self, need_rows=False):
@@ -551,23 +630,29 @@ def loader_cache_view(device, loader, fallback_scope=None, budget_bytes=None):
 class StepBatch:
     """`n` bags of a loader, in loader order. staged: their rows sit back to back in the staging slab (xs[j][0] are views of it; a zero-copy
     step slab, with `_advmil_stager_planes` on the first view when every bag came out of the cache with its operand planes)."""
-    __slots__ = ("pos", "idx", "xs", "ys", "staged", "pad")
+    __slots__ = ("pos", "idx", "xs", "ys", "staged", "pad", "keeps")
 
-    def __init__(self, pos, idx, xs, ys, staged, pad=0):
+    def __init__(self, pos, idx, xs, ys, staged, pad=0, keeps=None):
         self.pos, self.idx, self.xs, self.ys, self.staged, self.pad = pos, idx, xs, ys, staged, pad   # pad: zero rows behind the bags
+        # keeps (step_batches(mask=...)): per bag, the kept region indices of its instance mask or None. A STAGED batch is masked
+        # already (by the staging launch); the bags of an unstaged one are still clean -- the consumer applies `keeps` itself.
+        self.keeps = keeps
 
 
 def step_batches(loader, device, nb, cache=None, stager=None, drop_last=False, stageable=None, group_unstaged=False, pad_multiple=0,
-                 x_storage=None):
+                 x_storage=None, mask=None):
     """Walk `loader` ((idx, [x, ext], y) items, x[1, N, C] on the host) in step batches of `nb` bags whose rows are contiguous in HBM:
     host bags through the pinned staging slab on the copy stream, bags seen before out of the device-resident cache (device-to-
     device, on the copy stream too). Items `stageable(x)` rejects (device tensors, graphs, odd shapes) come as single-bag batches with
     staged = False, in order (`group_unstaged`: grouped `nb` at a time as well, for a training loop whose loader hands over device
     tensors). The consumer must have ENQUEUED its work on a batch before asking for the next one: the code behind
-    the `yield` then keeps first-seen bags in the cache and lets the staging slab be rewritten once that work has run."""
+    the `yield` then keeps first-seen bags in the cache and lets the staging slab be rewritten once that work has run.
+    `mask`: callable(n_rows) -> kept region indices (utils.func.square_instance_keep) or None, called once per bag in loader order,
+    for staged and unstaged items alike (StepBatch.keeps). A staged bag is masked by its staging launch; the cache holds the CLEAN
+    bag: a first-visit bag is copied into the cache on the copy stream before it is masked where it lies in the slab."""
     device = torch.device(device)
-    pos, idxs, xs, ys, fresh = [], [], [], [], []
-    loose = StepBatch([], [], [], [], False)      # unstaged items being grouped (group_unstaged)
+    pos, idxs, xs, ys, fresh, keeps = [], [], [], [], [], []
+    loose = StepBatch([], [], [], [], False, keeps=[] if mask is not None else None)      # unstaged items being grouped (group_unstaged)
     own = stager
 
     def ok(x0):
@@ -583,16 +668,17 @@ def step_batches(loader, device, nb, cache=None, stager=None, drop_last=False, s
             xs[0][0]._advmil_stager_planes = bpl
             if own.stale:
                 xs[0][0]._advmil_fp32_stale = True       # cached bags were staged as operand planes only: the slab's fp32 rows are not valid
-        return StepBatch(list(pos), list(idxs), list(xs), list(ys), True, pad)
+        return StepBatch(list(pos), list(idxs), list(xs), list(ys), True, pad, list(keeps) if mask is not None else None)
 
     def after():
         for key, j, fp in fresh:
             cache.put(key, xs[j][0], fp)
         own.release()
-        del pos[:], idxs[:], xs[:], ys[:], fresh[:]
+        del pos[:], idxs[:], xs[:], ys[:], fresh[:], keeps[:]
 
     for b, (idx, x, y) in enumerate(loader):
         x0 = x[0]
+        keep = mask(x0.shape[-2]) if mask is not None and torch.is_tensor(x0) and x0.dim() >= 2 else None
         if nb <= 1 or not ok(x0):
             if xs:
                 if drop_last and group_unstaged:  # (a step batch is `nb` bags of ONE kind; a training loop never mixes them)
@@ -601,11 +687,13 @@ def step_batches(loader, device, nb, cache=None, stager=None, drop_last=False, s
                 after()
             if group_unstaged and nb > 1:
                 loose.pos.append(b); loose.idx.append(idx); loose.xs.append(list(x)); loose.ys.append(y)
+                if mask is not None:
+                    loose.keeps.append(keep)
                 if len(loose.xs) == nb:
                     yield loose
-                    loose = StepBatch([], [], [], [], False)
+                    loose = StepBatch([], [], [], [], False, keeps=[] if mask is not None else None)
             else:
-                yield StepBatch([b], [idx], [list(x)], [y], False)
+                yield StepBatch([b], [idx], [list(x)], [y], False, keeps=[keep] if mask is not None else None)
             continue
         if loose.xs:
             raise ValueError("step_batches: host and device bags alternate inside one step batch")
@@ -622,11 +710,16 @@ def step_batches(loader, device, nb, cache=None, stager=None, drop_last=False, s
         if hit is not None:
             # the entry keeps its event: ANY copy stream that reads it (the handler's stager, the evaluation's) is ordered behind
             # the kernels that made it; waiting on a completed event costs nothing
-            v = own.add_device(hit, hit.__dict__.get("_advmil_bag_planes"), hit.__dict__.get("_advmil_ready"))
+            v = own.add_device(hit, hit.__dict__.get("_advmil_bag_planes"), hit.__dict__.get("_advmil_ready"), keep=keep)
+        elif keep is not None:
+            # a masked first visit: the clean bag goes into the cache on the copy stream, between its H2D copy and the masking launch
+            # (after() would keep the masked view)
+            v = own.add(x0, keep=keep, on_clean=None if cache is None else (lambda view, key=key, fp=fp: cache.put(key, view, fp)))
         else:
             if cache is not None:
                 fresh.append((key, len(xs), fp))
             v = own.add(x0)
+        keeps.append(keep)
         pos.append(b); idxs.append(idx); xs.append([v] + list(x[1:])); ys.append(y)
         if len(xs) == nb:
             yield finish()

@@ -146,13 +146,18 @@ class BaselineHandler(object):
 
     # ------------------------------------------------------------------------------------------
     @staticmethod
-    def test_model(model, backbone, loader, times_test_sample=1, checkpoint=None, batch_bags=None, x_storage=None):
+    def test_model(model, backbone, loader, times_test_sample=1, checkpoint=None, batch_bags=None, x_storage=None, mask_ratio=None,
+                   mask_rng=None):
         """443-487. The network has no noise, so in eval mode the `times_test_sample` repeated forwards of the reference are
         identical: a bag is run once and the sample axis is filled with that prediction. `batch_bags` (default 16,
         ADVMIL_EVAL_BATCH_BAGS) host bags are evaluated as one step slab, staged on the copy stream and kept in the device-resident
-        bag cache between epochs (as MyHandler.test_model); device tensors, graphs and batch_bags=1 take the per-bag loop."""
+        bag cache between epochs (as MyHandler.test_model); device tensors, graphs and batch_bags=1 take the per-bag loop.
+        `mask_ratio`, `mask_rng`: the occlusion-robustness test on clean resident bags, as MyHandler.test_model (baseline_handler.py:215
+        `exec_test` with test_mask_ratio): staged batches are masked by their staging launch, per-bag items on the device."""
         from ..ingest import loader_cache_view, step_batches
+        from ..utils.func import mask_square_rows, square_mask_fn
         from .model_handler import MyHandler
+        mask = square_mask_fn(backbone, mask_ratio, mask_rng)
         dev = next(model.parameters()).device
         if checkpoint is not None:
             model.load_state_dict(torch.load(checkpoint, map_location=dev)["model"])
@@ -163,7 +168,7 @@ class BaselineHandler(object):
         idxs, ys, preds = [], [], []
         with torch.no_grad():
             for bt in step_batches(loader, dev, nb, loader_cache_view(dev, loader), pad_multiple=int(os.environ.get("ADVMIL_SLAB_PAD", "256")),
-                                   x_storage=x_storage if x_storage is not None else getattr(model, "_advmil_x_storage", None)):
+                                   x_storage=x_storage if x_storage is not None else getattr(model, "_advmil_x_storage", None), mask=mask):
                 if bt.staged:
                     xs, pad = bt.xs, bt.pad
                     X = MyHandler._slab_build_static(xs, True, pad)
@@ -175,6 +180,8 @@ class BaselineHandler(object):
                     y_hat = model.finish(model.features_multi(X, seg, exts)[:len(xs)])
                 else:
                     x_data, x_ext = [t.to(dev) if torch.is_tensor(t) else t for t in bt.xs[0]]
+                    if bt.keeps is not None and bt.keeps[0] is not None:
+                        x_data = mask_square_rows(x_data[0], bt.keeps[0]).unsqueeze(0)
                     if backbone == "graph":
                         y_hat = model(x_ext, None)
                     elif backbone == "patch":

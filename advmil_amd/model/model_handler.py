@@ -31,7 +31,7 @@ from ..loss.utils import fake_generator_loss, real_fake_loss, real_fake_terms, r
 from ..optim import FlatAdam, create_optimizer
 from ..ingest import BagCache, SlabStager, bag_fingerprint, x_store_dtype
 from ..parallel import BagParallel
-from ..utils.func import agg_tensor, seed_everything, sparse_key, sparse_str
+from ..utils.func import agg_tensor, mask_square_rows, seed_everything, sparse_key, sparse_str, square_mask_fn
 from .backbone import load_backbone
 from .GANSurv import Discriminator, Generator, PrjDiscriminator
 from .model_utils import init_weights
@@ -1020,7 +1020,7 @@ class MyHandler(object):
     # ------------------------------------------------------------------------------------------
     @staticmethod
     def test_model(modelG, modelD, backbone, loader, times_test_sample=1, checkpoints=None, test_zero_noise=False, noise=None,
-                   batch_bags=None, x_storage=None):
+                   batch_bags=None, x_storage=None, mask_ratio=None, mask_rng=None):
         """Eval: y_hat, f_fake, and `times_test_sample` more generator samples + their median per bag (reference
         model_handler.py:598-643: one synchronous `.cuda()`, 1 + times_test_sample full generator forwards, one D forward and
         4-6 `.cpu()` syncs PER BAG -- and `_run_training` runs it over the validation and the test set after every epoch).
@@ -1030,7 +1030,14 @@ class MyHandler(object):
         double-buffered slab on the copy stream and kept in the device-resident bag cache across epochs (keyed by the loader's
         dataset object and patient index, shared budget with the training loop). The collector comes back with one D2H per key.
         PatchGCN bags, bags whose length is not a multiple of 16 and injected-noise calls with ragged lists take the per-bag path.
-        `noise`: optional per-bag list of injected noise tensors (tests)."""
+        `noise`: optional per-bag list of injected noise tensors (tests).
+        `mask_ratio` (the occlusion-robustness test, reference model_handler.py:189-224 with cfg test_mask_ratio): zero that share of
+        every bag's 4x4 square instances, as the reference's dataset does on the host (dataset/PatchWSI.py:80-81 ->
+        utils/func.py:14-40) -- here on the device, on a loader of CLEAN bags, so the bags stay in the resident cache: staged batches
+        are masked by their staging launch, per-bag items by indexing on the device. One draw per bag in loader order on every path,
+        from `mask_rng` (np.random.RandomState) or the global np.random. None, <= 0 or > 1: today's call, no draw. `cluster` and
+        `graph` bags are evaluated unmasked with one warning (the reference's dataset never masks them: PatchWSI.py:85-107)."""
+        mask = square_mask_fn(backbone, mask_ratio, mask_rng)
         if checkpoints is not None:
             dev = next(modelG.parameters()).device
             modelG.load_state_dict(torch.load(checkpoints[0], map_location=dev)["model"])
@@ -1041,8 +1048,10 @@ class MyHandler(object):
         keys = ["idx", "y", "y_hat", "f_fake"] + (["dist_y_hat", "avg_y_hat"] if times_test_sample > 1 else [])
         parts = {k: [] for k in keys}                 # device (or host, for idx / y) pieces in loader order; ONE .cpu() per key at the end
 
-        def one_bag(b, idx, x, y):
+        def one_bag(b, idx, x, y, keep=None):
             x_data, x_ext = [t.to(dev) if torch.is_tensor(t) else t for t in x]
+            if keep is not None:
+                x_data = mask_square_rows(x_data[0], keep).unsqueeze(0)
             if backbone == "graph":
                 H = modelG.backbone(x_ext, None)
             elif backbone == "patch":
@@ -1093,11 +1102,11 @@ class MyHandler(object):
         with torch.no_grad():
             for bt in step_batches(loader, dev, nb_max if slab_able else 1, loader_cache_view(dev, loader),
                                    stageable=lambda x0: x0.shape[1] % 16 == 0, pad_multiple=int(os.environ.get("ADVMIL_SLAB_PAD", "256")),
-                                   x_storage=x_storage):
+                                   x_storage=x_storage, mask=mask):
                 if bt.staged:
                     slab_batch(bt)
                 else:
-                    one_bag(bt.pos[0], bt.idx[0], bt.xs[0], bt.ys[0])
+                    one_bag(bt.pos[0], bt.idx[0], bt.xs[0], bt.ys[0], None if bt.keeps is None else bt.keeps[0])
         res = {k: None for k in ("idx", "y", "y_hat", "f_fake")}
         if parts["idx"]:
             res = {k: torch.cat([t if t.dim() > 0 else t.reshape(1) for t in parts[k]], dim=0).detach().cpu() for k in keys}

@@ -462,6 +462,17 @@ int advmil_optim_step(const advmil_optim_t* a, advmil_stream_t stream);
  * form (split in place of rows that just arrived over PCIe). */
 int advmil_stage_bag(void* dst_rows, const void* src_rows, size_t rows_bytes, void* dst_hi, const void* src_hi, void* dst_lo,
                      const void* src_lo, size_t plane_bytes, advmil_stream_t stream);
+/* advmil_stage_bag under a keep bitmap over the bag's 4x4 "square instances" (utils/func.py:14-40 random_mask_square_instance, way
+ * mask_zero, applied on the device to the resident clean bag instead of by the dataset on the host: dataset/PatchWSI.py:80-81).
+ * n_rows: rows of the bag, a multiple of 16; region r = rows [16 r, 16 r + 16) is kept when bit r & 31 of keep_bits[r >> 5] is set
+ * (device array of ceil(n_rows / 16 / 32) words, 4-byte aligned). Kept regions are copied and their planes copied or derived exactly
+ * as by advmil_stage_bag; masked regions are written as zeros in the rows and in both planes and are never read from the source.
+ * Forms: rows + derived planes; the same with dst_rows = NULL (planes only: nothing is written but the planes; there is no
+ * dst == src convention for that here); rows + held planes copied; rows only (elements of any size: rows_bytes / n_rows is the row
+ * size); and in place, dst_rows == src_rows (kept regions stay, masked regions are zeroed, planes derived when asked for).
+ * Pointers 16-byte aligned, planes all or none; ADVMIL_EINVAL before any launch otherwise. */
+int advmil_stage_bag_masked(void* dst_rows, const void* src_rows, size_t rows_bytes, int64_t n_rows, void* dst_hi, const void* src_hi,
+                            void* dst_lo, const void* src_lo, size_t plane_bytes, const uint32_t* keep_bits, advmil_stream_t stream);
 /* fill out[i] = U[0,1) from the counter RNG (generator noise, utils/func.py:154-164) */
 int advmil_uniform_fill(float* out, int64_t n, const uint64_t* seed, uint64_t stream_id, const int64_t* rng_row, int64_t width,
                         advmil_stream_t stream);
