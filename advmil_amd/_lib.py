@@ -156,6 +156,12 @@ SIGNATURES = {
     "advmil_ln_relu_bwd_workspace_bytes": (c_size_t, [c_int64, c_int64]),
     "advmil_ln_relu_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p,
                                    c_void_p, c_void_p, c_int, c_void_p, c_size_t, c_void_p]),
+    "advmil_gcn_res_fwd": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_float, c_int64, c_int64, c_float, c_void_p,
+                                   c_uint64, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
+    "advmil_gcn_res_bwd_workspace_bytes": (c_size_t, [c_int64, c_int64]),
+    "advmil_gcn_res_bwd": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_float,
+                                   c_void_p, c_uint64, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_int,
+                                   c_void_p, c_size_t, c_void_p]),
     "advmil_gapool16_fwd": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_int, c_void_p]),
     "advmil_gapool16_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int, c_void_p, c_void_p, c_int, c_void_p]),
     "advmil_genconv_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_int64, c_int64, c_void_p, c_void_p,

@@ -1188,14 +1188,7 @@ extern "C" int advmil_colsum(const float* x, int64_t M, int64_t N, float* out, i
     else hipLaunchKernelGGL((kernel<8>), grid, dim3(256), 0, stream, __VA_ARGS__);                        \
   } while (0)
 
-// The rounded mean mu0 of a row leaves dm = mean(row - mu0) behind: round-off of a sum of d values of the row's magnitude, up to an ulp of
-// |mu0| (6e-5 for rows near 1e3), by which every normalised value of the row would be shifted, times rstd. The once-centred row is small, so
-// dm itself is exact to ITS round-off. Where that shift exceeds 2^-20 the row is centred by dm too (variance: mean c^2 - dm^2, the identity
-// for c = row - mu0); below it dm counts as 0 and every expression that takes it (c - dm, ve - dm * dm, mu0 + dm) is the uncorrected one
-// bit for bit -- rows whose mean is small against their spread, the shipped activations among them, keep their bits.
-__device__ __forceinline__ float ln_recentre(float dm, float ve /* variance + eps of the once-centred row */) {
-  return fabsf(dm) * hw_rsq(ve) > 0x1p-20f ? dm : 0.f;
-}
+// (ln_recentre, the second centring of rows with a large mean: common.h, shared with gcnres.hip)
 
 template <int QT>
 __global__ __launch_bounds__(256) void ln_relu_mean16_fwd_kernel(const float* __restrict__ y, const float* __restrict__ gamma,

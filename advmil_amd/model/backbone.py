@@ -30,9 +30,28 @@ def load_backbone_param(mode, dims):
     return [dims[:3]], {"dropout": 0.25}
 
 
-def load_backbone(mode, dims):
+_GRAPH_OVERRIDES = ("num_layers", "edge_agg")
+
+
+def load_backbone(mode, dims, **overrides):
+    """The reference's call; `num_layers` / `edge_agg` overrides reach PatchGCN's constructor (mode 'graph' only)."""
     args, kws = load_backbone_param(mode, dims)
+    for k in overrides:
+        if mode != "graph" or k not in _GRAPH_OVERRIDES:
+            raise TypeError(f"load_backbone: override '{k}' is not taken by mode '{mode}' (only 'graph' takes {_GRAPH_OVERRIDES})")
+    kws.update(overrides)
     return Model_Zoo(mode)(*args, **kws)
+
+
+def backbone_overrides(cfg):
+    """The handlers' two optional PatchGCN keys -> load_backbone overrides: cfg['bcb_gcn_layers'] (absent: 1, as shipped) and
+    cfg['bcb_gcn_edge_agg'] (absent: 'spatial'). Set under another bcb_mode they would be ignored without a word: ValueError."""
+    keys = {"bcb_gcn_layers": "num_layers", "bcb_gcn_edge_agg": "edge_agg"}
+    given = {arg: cfg[k] for k, arg in keys.items() if cfg.get(k) is not None}
+    if given and cfg["bcb_mode"] != "graph":
+        raise ValueError(f"{' / '.join(k for k in keys if cfg.get(k) is not None)} set with bcb_mode = '{cfg['bcb_mode']}': "
+                         "they configure PatchGCN (bcb_mode: graph) only")
+    return given
 
 
 def _small_fc(seq, x, rng, tag):
@@ -158,47 +177,57 @@ class _GENConvParams(nn.Module):
 
 
 class _DeepGCNLayerParams(nn.Module):
-    """DeepGCNLayer(conv, norm, act): only `conv` runs when num_layers == 1 (model/backbone.py:157); `norm` exists in
-    the reference's state_dict, so it exists here."""
+    """DeepGCNLayer(conv, norm, act, block='res', dropout=0.1): layer 0 runs `conv` only (model/backbone.py:157), so its `norm` is never
+    used; it exists in the reference's state_dict, so it exists here."""
 
     def __init__(self, dim):
         super().__init__()
         self.conv = _GENConvParams(dim)
         self.norm = nn.LayerNorm(dim, elementwise_affine=True)
         self.act = nn.ReLU(inplace=True)
+        self.drop = nn.Dropout(0.1)   # the reference's constant (model/backbone.py:142), not the backbone's `dropout`; no parameters
 
 
 class PatchGCN(nn.Module):
-    """FC -> GENConv(softmax aggr, learnable t) -> cat -> FC -> gated attention pool. `x_path` is a graph object with
-    `.x [N, dim_in]` and `.edge_index [2, E]` (a torch_geometric Batch in the reference; any object with those two
-    attributes here). Parity unpinned (GENConv's arithmetic is torch_geometric's, absent and unversioned)."""
+    """FC -> num_layers x GENConv(softmax aggr, learnable t), layers 1.. wrapped in the residual block
+    x + relu(LayerNorm(conv(x))) -> cat of every layer's output -> FC -> gated attention pool. `x_path` is a graph object with
+    `.x [N, dim_in]`, `.edge_index [2, E]` and, for edge_agg = 'latent', `.edge_latent [2, E']` (a torch_geometric Batch in the
+    reference; any object with those attributes here). Parity unpinned (the arithmetic of GENConv and DeepGCNLayer is
+    torch_geometric's, absent and unversioned)."""
 
     def __init__(self, dims: List, num_layers: int = 3, edge_agg: str = "spatial", dropout: float = 0.25):
         super().__init__()
         assert len(dims) == 3
         dim_in, dim_hid, dim_out = dims
-        if num_layers != 1:
-            raise NotImplementedError("HIP PatchGCN covers num_layers=1, the value load_backbone_param ships (backbone.py:40)")
+        if not isinstance(num_layers, int) or isinstance(num_layers, bool) or num_layers < 1:
+            raise ValueError(f"PatchGCN: num_layers = {num_layers!r}, must be an integer >= 1")
+        if edge_agg not in ("spatial", "latent"):
+            raise ValueError(f"PatchGCN: edge_agg = {edge_agg!r}, must be 'spatial' or 'latent'")
         self.edge_agg, self.num_layers = edge_agg, num_layers
         self.fc = nn.Sequential(nn.Linear(dim_in, dim_hid), nn.ReLU(), nn.Dropout(dropout))
         self.layers = nn.ModuleList([_DeepGCNLayerParams(dim_hid) for _ in range(num_layers)])
         self.path_phi = nn.Sequential(nn.Linear(dim_hid * (1 + num_layers), dim_out), nn.ReLU(), nn.Dropout(dropout))
         self.path_attention_head = Attn_Net_Gated(L=dim_out, D=dim_out, dropout=dropout, n_classes=1)
 
+    @property
+    def _edges(self):
+        return "edge_index" if self.edge_agg == "spatial" else "edge_latent"
+
     def features_multi(self, X, seg=None, exts=None):
-        """Slab form: the bags' graphs become one block-diagonal graph over the slab's rows (node ids offset per bag)."""
+        """Slab form: the bags' graphs become one block-diagonal graph over the slab's rows (node ids offset per bag), built from
+        the edge set in use."""
         if seg is None:
             return self.forward(exts[0])
-        # one union CSR per distinct group of graphs, kept alive for the module's lifetime: captured HIP graphs hold the
-        # raw addresses of these index arrays
-        key = tuple(id(e) for e in exts)
+        # one union CSR per distinct group of graphs and edge set, kept alive for the module's lifetime: captured HIP graphs hold
+        # the raw addresses of these index arrays
+        which = self._edges
+        key = (self.edge_agg,) + tuple(id(e) for e in exts)
         caches = self.__dict__.setdefault("_union_cache", {})
         cache = caches.get(key)
         if cache is None:
-            ei = torch.cat([e.edge_index.to(torch.long) + seg.offsets[b] for b, e in enumerate(exts)], dim=1)
-            from types import SimpleNamespace
-            union = SimpleNamespace(x=X, edge_index=ei)
-            union._advmil_csr = ops.GraphCSR(ei, seg.total)
+            ei = torch.cat([getattr(e, which).to(torch.long) + seg.offsets[b] for b, e in enumerate(exts)], dim=1)
+            union = SimpleNamespace(x=X, **{which: ei})
+            setattr(union, ops.CSR_ATTR[which], ops.GraphCSR(ei, seg.total))
             caches[key] = cache = (key, union, list(exts))
         union = cache[1]
         union.x = X
@@ -207,18 +236,26 @@ class PatchGCN(nn.Module):
     def forward(self, x_path, *args):
         return self._run(x_path, None)
 
+    def _conv(self, conv, x, csr):
+        """GENConv: softmax aggregation + x, then its Linear -> LayerNorm -> ReLU -> Linear."""
+        agg = ops.genconv_aggregate(x, conv.t, csr, conv.eps)
+        hmid = ops.linear_act(agg, conv.mlp[0].weight, conv.mlp[0].bias, "none")
+        hmid = ops.ln_relu(hmid, conv.mlp[1].weight, conv.mlp[1].bias, conv.mlp[1].eps)
+        return ops.linear_act(hmid, conv.mlp[4].weight, conv.mlp[4].bias, "none")
+
     def _run(self, data, seg):
         x_in = data.x
         rng = _rng_of(self, x_in)
         tr = self.training
-        csr = ops.graph_csr(data)
+        csr = ops.graph_csr(data, self._edges)
         x = ops.linear_act(x_in, self.fc[0].weight, self.fc[0].bias, "relu", self.fc[2].p if tr else 0.0, rng, "gcn_fc")
-        conv = self.layers[0].conv
-        agg = ops.genconv_aggregate(x, conv.t, csr, conv.eps)
-        hmid = ops.linear_act(agg, conv.mlp[0].weight, conv.mlp[0].bias, "none")
-        hmid = ops.ln_relu(hmid, conv.mlp[1].weight, conv.mlp[1].bias, conv.mlp[1].eps)
-        x1 = ops.linear_act(hmid, conv.mlp[4].weight, conv.mlp[4].bias, "none")
-        h = torch.cat([x, x1], dim=1)
+        xs = [x, self._conv(self.layers[0].conv, x, csr)]
+        for l in range(1, self.num_layers):
+            layer = self.layers[l]
+            h = self._conv(layer.conv, xs[-1], csr)
+            xs.append(ops.gcn_res(h, xs[-1], layer.norm.weight, layer.norm.bias, layer.norm.eps, layer.drop.p if tr else 0.0, rng,
+                                  f"gcn_res{l}"))
+        h = torch.cat(xs, dim=1)
         h = ops.linear_act(h, self.path_phi[0].weight, self.path_phi[0].bias, "relu", self.path_phi[2].p if tr else 0.0, rng, "gcn_phi")
         pooled, A, _ = self.path_attention_head.pool(h, seg)
         self.last_attention = A.detach()

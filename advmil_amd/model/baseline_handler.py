@@ -14,7 +14,7 @@ from .. import ops
 from ..loss.utils import MSE_loss, SurvMLE, SurvPLE, recon_loss
 from ..optim import create_optimizer
 from ..utils.func import agg_tensor, seed_everything, sparse_key, sparse_str
-from .backbone import load_backbone
+from .backbone import backbone_overrides, load_backbone
 from .BaseSurv import SurvNet
 from .model_utils import general_init_weight, init_weights
 
@@ -23,6 +23,7 @@ class BaselineHandler(object):
     def __init__(self, cfg, device=None):
         assert cfg["task"] in ["surv_cox", "surv_nll", "surv_reg"]
         assert cfg["bcb_mode"] in ["patch", "cluster", "graph", "abmil"]
+        bcb_overrides = backbone_overrides(cfg)
         if device is None:
             if torch.cuda.device_count() == 0:
                 raise RuntimeError("advmil_amd.BaselineHandler needs an MI355X: no ROCm device visible (no CPU fallback)")
@@ -40,7 +41,7 @@ class BaselineHandler(object):
         # out_scale / time format follow the task (baseline_handler.py:68-78)
         out_scale = "none" if self.task == "surv_cox" else "sigmoid"
         cfg["time_format"] = {"surv_nll": "quantile", "surv_reg": "ratio", "surv_cox": "origin"}[self.task]
-        backbone = load_backbone(self.bcb, sparse_str(cfg["bcb_dims"]))
+        backbone = load_backbone(self.bcb, sparse_str(cfg["bcb_dims"]), **bcb_overrides)
         dim_in, dim_out = sparse_str(cfg["pdh_dims"])
         self.net = SurvNet(dim_in, dim_out, backbone, hops=cfg["mlp_hops"], norm=cfg["mlp_norm"], dropout=cfg["mlp_dropout"],
                            out_scale=out_scale)

@@ -32,7 +32,7 @@ from ..optim import FlatAdam, create_optimizer
 from ..ingest import BagCache, SlabStager, bag_fingerprint, x_store_dtype
 from ..parallel import BagParallel
 from ..utils.func import agg_tensor, mask_square_rows, seed_everything, sparse_key, sparse_str, square_mask_fn
-from .backbone import load_backbone
+from .backbone import backbone_overrides, load_backbone
 from .GANSurv import Discriminator, Generator, PrjDiscriminator
 from .model_utils import init_weights
 
@@ -195,6 +195,7 @@ class StaticStepPlan:
 class MyHandler(object):
     def __init__(self, cfg, device=None, parallel=None):
         _check_configs(cfg)
+        bcb_overrides = backbone_overrides(cfg)
         if device is None:
             ndev = torch.cuda.device_count()
             if ndev == 0:
@@ -239,7 +240,7 @@ class MyHandler(object):
             self.best_netG_ckpt_path = osp.join(save_path, "modelG-best.pth")
 
         # ---- networks (model_handler.py:70-91)
-        backbone = load_backbone(self.bcb, sparse_str(cfg["bcb_dims"]))
+        backbone = load_backbone(self.bcb, sparse_str(cfg["bcb_dims"]), **bcb_overrides)
         dim_in, dim_out = sparse_str(cfg["gen_dims"])
         args_noise = SimpleNamespace(**sparse_key(cfg, prefixes="gen_noi"))
         args_noise.noise = sparse_str(args_noise.noise)

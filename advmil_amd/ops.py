@@ -229,7 +229,7 @@ class DeviceRng:
 # one site never share a row count (L vs 2L, n vs 2n, sum N >= 16 n vs 8 n), so (site, row count) identifies the map even when
 # two DIFFERENT layouts of a step happen to have equally many rows (e.g. 2n == sum N / 16 for two 32-patch bags).
 SITE_LAYOUTS = {
-    "abmil_fc": ("patch",), "gcn_fc": ("patch",), "gcn_phi": ("patch",), "gate_": ("patch", "cluster"),
+    "abmil_fc": ("patch",), "gcn_fc": ("patch",), "gcn_phi": ("patch",), "gcn_res": ("patch",), "gate_": ("patch", "cluster"),
     "abmil_rho": ("bag",), "misl_fc": ("cluster",), "gapool_": ("region", "region2"), "esat_": ("region",),
     "dx_fc1": ("region", "region2"), "dx_fc2": ("bag", "bag2"), "dy": ("bag", "bag2"), "gen_mlp": ("bag",), "noise": ("bag",),
     "surv_mlp": ("bag",),
@@ -2085,6 +2085,66 @@ def ln_relu(y, gamma, beta, eps=1e-5):
     return LNReLUFn.apply(y, gamma, beta, eps)
 
 
+class GcnResFn(torch.autograd.Function):
+    """out = dropout_p(x + relu(LayerNorm(h))): the residual block between the GENConv layers of a deep PatchGCN (DeepGCNLayer 'res',
+    reference model/backbone.py:160-167) as one launch each way (csrc/gcnres.hip); dropout index = row*d + col on stream `sid`, drawn
+    again by the backward."""
+
+    @staticmethod
+    def forward(ctx, h, x, gamma, beta, eps, p, seed, sid, rr=None):
+        _chk(h, "h"); _chk(x, "x")
+        h = h.contiguous()
+        if x.dim() != 2 or x.stride(1) != 1 or x.stride(0) % 4 or x.stride(0) < x.shape[1] or x.data_ptr() % 16:
+            x = x.contiguous()
+        N, d = h.shape
+        if x.shape != h.shape:
+            raise ValueError(f"gcn_res: x {tuple(x.shape)} against h {tuple(h.shape)}")
+        out = torch.empty_like(h)
+        mean = torch.empty(N, dtype=torch.float32, device=h.device)
+        rstd = torch.empty(N, dtype=torch.float32, device=h.device)
+        g_, b_ = gamma.detach(), beta.detach()
+        if p <= 0.0:
+            seed = rr = None
+        elif rr is not None and rr.data_ptr() % 16:
+            rr = rr.clone()
+        _lib.check(_lib.lib().advmil_gcn_res_fwd(_p(h), _p(x), x.stride(0), _p(g_), _p(b_), eps, N, d, p, _p(seed), sid, _p(rr), _p(out), d,
+                                                 _p(mean), _p(rstd), _stream()), "gcn_res_fwd")
+        ctx.save_for_backward(h, g_, b_, mean, rstd)
+        ctx.cfg = (p, seed, sid, rr)
+        gg, gb = _arena_grad(gamma), _arena_grad(beta)
+        ctx.arena = (gg, gb) if (gg is not None and gb is not None) else None
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        h, gamma, beta, mean, rstd = ctx.saved_tensors
+        p, seed, sid, rr = ctx.cfg
+        N, d = h.shape
+        L = _lib.lib()
+        if dout.stride(1) != 1 or dout.stride(0) % 4 or dout.stride(0) < d or dout.data_ptr() % 16:
+            dout = dout.contiguous()
+        dh = torch.empty_like(h)
+        dx = torch.empty_like(h)
+        acc = ctx.arena is not None
+        dg = ctx.arena[0] if acc else torch.empty(d, dtype=torch.float32, device=h.device)
+        db = ctx.arena[1] if acc else torch.empty(d, dtype=torch.float32, device=h.device)
+        wsb = L.advmil_gcn_res_bwd_workspace_bytes(N, d)
+        ws = _ws(wsb, h.device)
+        _lib.check(L.advmil_gcn_res_bwd(_p(dout), dout.stride(0), _p(h), _p(gamma), _p(beta), _p(mean), _p(rstd), N, d, p, _p(seed), sid,
+                                        _p(rr), _p(dh), _p(dx), d, 0, _p(dg), _p(db), 1 if acc else 0, _p(ws), wsb, _stream()),
+                   "gcn_res_bwd")
+        return (dh, dx, None, None, None, None, None, None, None) if acc else (dh, dx, dg, db, None, None, None, None, None)
+
+
+def gcn_res(h, x, gamma, beta, eps=1e-5, p=0.0, rng=None, tag="gcn_res"):
+    """x + relu(LayerNorm(h)) with train-mode dropout p over the sum, drawn at a fresh call site `tag` (layer l: gcn_res{l})."""
+    sid, seed, rr = 0, None, None
+    if p > 0.0:
+        rng = rng or default_rng(h.device)
+        sid, seed, rr = rng.site(tag, tuple(h.shape), p), rng.seed, rng.row_map(h.shape[0], tag)
+    return GcnResFn.apply(h, x, gamma, beta, float(eps), float(p), seed, sid, rr)
+
+
 class GAPool16Fn(torch.autograd.Function):
     """Gated-attention pooling of each consecutive 16 rows (GAPoolPatchEmbedding's tail, model/backbone_utils.py:197-201):
     s[N] raw scores, z[N,d] -> (emb[dup N/16, d], A[N]). One launch each way (csrc/gapool16.hip): the segment of a row is row >> 4, so
@@ -2148,13 +2208,17 @@ class GraphCSR:
         return rowptr.contiguous(), val[order].to(torch.int32).contiguous()
 
 
-def graph_csr(data):
-    """Cached GraphCSR of a graph object with `.edge_index` (and `.x`)."""
-    g = getattr(data, "_advmil_csr", None)
+CSR_ATTR = {"edge_index": "_advmil_csr", "edge_latent": "_advmil_csr_latent"}
+
+
+def graph_csr(data, which="edge_index"):
+    """Cached GraphCSR of one edge set (`.edge_index` or `.edge_latent`) of a graph object with `.x`; one cache attribute per set."""
+    attr = CSR_ATTR[which]
+    g = getattr(data, attr, None)
     if g is None:
-        g = GraphCSR(data.edge_index, data.x.shape[0])
+        g = GraphCSR(getattr(data, which), data.x.shape[0])
         try:
-            data._advmil_csr = g
+            setattr(data, attr, g)
         except Exception:
             pass
     return g

@@ -357,6 +357,27 @@ int advmil_ln_relu_bwd(const float* dout, const float* y, const float* gamma, co
                        void* ws, size_t ws_bytes, advmil_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Residual block between the GENConv layers of a deep PatchGCN (DeepGCNLayer, block 'res'; model/backbone.py:148-168):
+ *   out = keep / (1 - p) * (x + relu(LayerNorm(h)))      h[N, d] contiguous; x (row pitch ldx) and out (row pitch ldo) may be column
+ *   blocks of a wider buffer. fwd also writes mean[N] and rstd[N] of h's rows for the backward.
+ * The keep decision of element (m, n) is drawn at (seed, stream_id, rng_row[m] * d + n) (rng_row NULL: m) with the hash of
+ * advmil_dropout_apply; the backward draws it again and stores no mask.
+ * bwd: g = dout * keep / (1 - p) (dout: row pitch lddo); dx (row pitch lddx) = g, added onto dx when dx_accumulate != 0;
+ *   dh[N, d] = LayerNorm'(g * (LayerNorm(h) > 0)); dgamma / dbeta = the column sums, through per-workgroup partial rows in ws merged
+ *   in a fixed order (accumulate != 0 adds into them). ws >= advmil_gcn_res_bwd_workspace_bytes (a pure host function).
+ * One row kernel each way, no host synchronisation (capturable).
+ * Shapes: N > 0; 4 <= d <= 512 with d % 4 == 0; every pitch >= d and % 4 == 0; every pointer 16-byte aligned; 0 <= drop_p < 1, and
+ * drop_p > 0 needs seed. Anything else: ADVMIL_EINVAL before any launch. */
+int advmil_gcn_res_fwd(const float* h, const float* x, int64_t ldx, const float* gamma, const float* beta, float eps, int64_t N,
+                       int64_t d, float drop_p, const uint64_t* seed, uint64_t stream_id, const int64_t* rng_row, float* out,
+                       int64_t ldo, float* mean, float* rstd, advmil_stream_t stream);
+size_t advmil_gcn_res_bwd_workspace_bytes(int64_t N, int64_t d);
+int advmil_gcn_res_bwd(const float* dout, int64_t lddo, const float* h, const float* gamma, const float* beta, const float* mean,
+                       const float* rstd, int64_t N, int64_t d, float drop_p, const uint64_t* seed, uint64_t stream_id,
+                       const int64_t* rng_row, float* dh, float* dx, int64_t lddx, int dx_accumulate, float* dgamma, float* dbeta,
+                       int accumulate, void* ws, size_t ws_bytes, advmil_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Region embedding tail of GAPoolPatchEmbedding (model/backbone_utils.py:171-202): gated-attention pooling of each consecutive 16
  * rows. s[N] = the rows' raw gate scores, z[N,d] (row pitch ldz) = the rows that are pooled (relu(LayerNorm(FC x))); region r is rows
  * [16 r, 16 r + 16), R = N / 16:
