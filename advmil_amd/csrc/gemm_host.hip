@@ -288,6 +288,10 @@ extern "C" int advmil_gemm_f32_tiled(int a_kc, int b_kc, int64_t M, int64_t N, i
       if (!plain || epi->n_split <= 0 || epi->n_split >= N || (epi->n_split & 31) || (epi->ldc2 & 3) || ((uintptr_t)epi->c2 & 15) ||
           epi->act_split != epi->n_split)
         return ADVMIL_EINVAL;
+      // only the plain STREAMING epilogue routes the second layer's columns to c2 (the generic fallback would store them into C behind
+      // column n_split, past the end of its last row): everything else that form asks for
+      if ((ldc & 3) || (((uintptr_t)C) & 15) || (((uintptr_t)epi->bias) & 15) || (epi->c_hi && ((((uintptr_t)epi->c_hi) | ((uintptr_t)epi->c_lo)) & 7)))
+        return ADVMIL_EINVAL;
     }
     if (g_gemm_mode != 1 || !a_kc || !b_kc || pre != 3 || splits != 1 || (M % bm) || (K % bkt) || (N % (64 * tnp))) return ADVMIL_EINVAL;
     if (epi->gate_wc && (!epi->gate_out || (epi->drop_p > 0.0f && !gate_store) || epi->gate_np != advmil_gemm_f32_gate_blocks(tile, N))) return ADVMIL_EINVAL;

@@ -633,8 +633,11 @@ def gemm(A, B, a_kc, b_kc, M, N, K, out=None, ldc=None, bias=None, act0=0, act1=
         # right for the optimizer's gradient arena, which nothing reads before the step, wrong for any other destination -- the next
         # launch would read C without the partials. Such a call takes the fold-free plan.
         splits = 1
-    if b_only and not (91 <= tile <= 93) and tile not in (22, 12, 11) and not (tile in (34, 24) and not a_kc and not b_kc):
-        tile = 22                             # a bf16 / planes-only B operand has no fp32 image: land on a kernel that stages B from its plane(s)
+    if (b_only and not (91 <= tile <= 93) and not (82 <= tile <= 86 and not b_single) and tile not in (22, 12, 11)
+            and not (tile in (34, 24) and not a_kc and not b_kc)):
+        # a bf16 / planes-only B operand has no fp32 image: land on a kernel that stages B from its plane(s). (82-86 read two-plane
+        # operands from their planes and nothing else: a B whose fp32 image is stale stays there, as B=None does)
+        tile = 22
     if planes_only_a and a_planes.single and not (82 <= tile <= 86) and tile not in (22, 12, 11):
         tile = 22                             # (single-plane A: only these forms are built for it)
     if planes_only_a and a_planes.fp32_stale and not (82 <= tile <= 86) and not (91 <= tile <= 93) and tile not in (22, 12, 11) \

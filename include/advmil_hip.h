@@ -96,7 +96,8 @@ typedef struct {
   /* Two layers over the same rows in one launch (plane-fed NT form, tile 85 only): B holds both layers' weight rows stacked
    * ([N, K]: layer 1 first); columns [0, n_split) of the product are layer 1 -- bias, output C (pitch ldc), planes c_hi/c_lo --,
    * columns [n_split, N) are layer 2 -- bias2[n - n_split], output c2[m*ldc2 + n - n_split], no planes. act_split = n_split selects
-   * the two activations. n_split % 32 == 0; c2 = NULL = an ordinary launch. The generator's and the discriminator's first layers
+   * the two activations. n_split % 32 == 0; C, c2 and bias 16-byte aligned, ldc % 4 == 0 and ldc2 % 4 == 0, c_hi / c_lo 8-byte aligned
+   * (ADVMIL_EINVAL otherwise: only the streaming epilogue routes layer 2); c2 = NULL = an ordinary launch. The generator's and the discriminator's first layers
    * over the step slab read X once this way (model/backbone.py:60-66 + model/model_utils.py:130-140). */
   float* c2;
   int64_t ldc2;

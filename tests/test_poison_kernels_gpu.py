@@ -27,6 +27,7 @@ from advmil_amd import synth
 from tests import helpers as H
 from tests import poison as P
 from tests import test_attention_gpu as TA
+from tests import test_gemm_walks_gpu as TW
 from tests import test_genconv_gpu as TG
 from tests import test_kernels_gpu as TK
 from tests import test_row_walks_gpu as TR
@@ -580,6 +581,38 @@ def test_row_kernel_walks(ops, launch, body, case):
     once more through its family's float64 body while the allocations are poisoned."""
     runs(lambda: launch(case))
     under_ff(body, case)
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# the walks of the plane-fed contraction kernels (tests/test_gemm_walks_gpu.py): one case of each family
+# ------------------------------------------------------------------------------------------------------------------------------
+GEMM_WALKS = [
+    # persistent NT kernel, single-plane A (the epilogue's LDS area lies behind the ring), rank-1 term + bit mask + column sums, pitches > extent
+    TW.Case("nt", 82, "NT", 768, 256, 96, 1, 2, 8, 24, ldc_pad=4, epi=TW.Epi(rowv=True, rowseg=True, maskbits=True, colsum=True), feed="stale"),
+    # the two-layer form with layer 1 as planes only (no fp32 C at all)
+    TW.Case("nt", 86, "NT", 768, 256, 64, 2, 2, 24, 8, epi=TW.two_layers(256, "only")),
+    # TN kernel: ten groups under a grid of sixteen (six workgroups leave at once), partial tiles in a fresh workspace, the reduce kernel
+    TW.Case("tn", 91, "TN", 640, 256, 224, 2, 1, splits=2, epi=TW.Epi(bias=True, act0=1)),
+    # ... a last split of one chunk under the three-slot ring, folded by the merge queue
+    TW.Case("tn", 92, "TN", 512, 128, 224, 2, 2, 8, 24, splits=3, epi=TW.Epi(accumulate=True)),
+    # register-staged planes: the predicated tail of the 192-row tile, ragged N and K, split-K
+    TW.Case("pre", 34, "TN", 192, 264, 264, 2, 2, b_pad=8, splits=3, epi=TW.Epi(accumulate=True), feed="stale"),
+    TW.Case("pre", 11, "TT", 200, 136, 72, 1, 2, splits=3, epi=TW.Epi(alpha=0.5, bias=True, act0=1)),
+]
+
+
+@pytest.mark.parametrize("case", GEMM_WALKS, ids=TW.case_id)
+def test_contraction_walks(ops, case):
+    """Each case asserts its walk on the host, runs four times for the bit comparison and once more against the exact oracle while the
+    allocations are poisoned (torch.equal: no tolerance)."""
+    runs(lambda: TW.launch(case))
+    under_ff(TW.body, case)
+
+
+def test_contraction_walk_gate_score_tile(ops):
+    case = TW.GATE_CASES[0]
+    runs(lambda: TW.launch_gate(case)[0])
+    under_ff(TW.test_plane_fed_gate_score_tile, case)
 
 
 # ------------------------------------------------------------------------------------------------------------------------------
