@@ -234,6 +234,10 @@ SIGNATURES = {
     "advmil_rank_loss_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_float, c_int, c_int, c_void_p, c_void_p, c_void_p, c_size_t,
                                      c_void_p]),
     "advmil_rank_loss_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_float, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "advmil_knn_spatial": (c_int, [c_void_p, c_int64, c_int, c_int, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
+    "advmil_knn_latent_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int]),
+    "advmil_knn_latent": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int, c_int, c_void_p, c_int64, c_void_p, c_void_p,
+                                  c_void_p, c_size_t, c_void_p]),
 }
 
 _lib = None

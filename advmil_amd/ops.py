@@ -2960,3 +2960,93 @@ def dx_region_pool(e, W1, b1, W2, b2, Wa, ba, Wb, bb, wc, bc, p1=0.0, pg=0.0, rn
     ps = (W1, b1, W2, b2, Wa, ba, Wb, bb, wc, bc)
     nograd = not torch.is_grad_enabled() or not (e.requires_grad or any(t.requires_grad for t in ps))
     return DxRegionPoolFn.apply(e, W1, b1, W2, b2, Wa, ba, Wb, bb, wc, bc, float(p1), float(pg), seed, sids, rr, seg, bool(want_mean), nograd)
+
+
+# ---------------------------------------------------------------------------------------
+# WSI graph construction: exact k-NN edges (advmil_knn_spatial / advmil_knn_latent, csrc/knn.hip); advmil_amd/wsigraph.py is the
+# public surface over these two
+# ---------------------------------------------------------------------------------------
+KNN_MAX_K = 16
+KNN_COORD_LIMIT = 1 << 30            # |coordinate| < 2^30: |dx| < 2^31, dx^2 + dy^2 < 2^63, exact in int64
+
+
+def _knn_check_bags(what, N, k, seg):
+    """The checks that need no device: k, the partition, and every bag longer than k (a row must HAVE k neighbours other than itself)."""
+    if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= KNN_MAX_K:
+        raise ValueError(f"advmil_amd: {what}: k = {k!r}, must be an integer in 1..{KNN_MAX_K}")
+    lens = [N] if seg is None else seg.lens
+    if sum(lens) != N:
+        raise ValueError(f"advmil_amd: {what}: the segments cover {sum(lens)} rows, the input has {N}")
+    for b, n in enumerate(lens):
+        if n <= k:
+            raise ValueError(f"advmil_amd: {what}: bag {b} has {n} rows, k = {k} neighbours other than the row itself need more than {k}")
+
+
+def knn_coords_int32(xy):
+    """Patch coordinates [N, 2] as the int32 tensor the spatial search reads. int32 / int64 tensors, and float tensors whose values
+    are integers (the reference stores `centroid` as float), are taken; anything else, a non-integer value or |c| >= 2^30 is a
+    ValueError. Reads the values back (one synchronisation): graph construction is preprocessing."""
+    if xy.dim() != 2 or xy.shape[1] != 2:
+        raise ValueError(f"advmil_amd: knn_spatial: coordinates must be [N, 2], got {tuple(xy.shape)}")
+    if xy.dtype in (torch.float32, torch.float64, torch.float16, torch.bfloat16):
+        if xy.numel() and not bool((torch.isfinite(xy) & (xy == xy.round())).all()):
+            raise ValueError("advmil_amd: knn_spatial: float coordinates must hold integer values")
+        if xy.numel() and float(xy.abs().max()) >= KNN_COORD_LIMIT:          # (checked as float: a value beyond int64 has no integer image)
+            raise ValueError("advmil_amd: knn_spatial: |coordinate| must be < 2^30")
+        c = xy.to(torch.int64)
+    elif xy.dtype in (torch.int32, torch.int64):
+        c = xy
+    else:
+        raise ValueError(f"advmil_amd: knn_spatial: coordinates must be int32, int64 or integer-valued float, got {xy.dtype}")
+    if c.numel() and (int(c.max()) >= KNN_COORD_LIMIT or int(c.min()) <= -KNN_COORD_LIMIT):
+        raise ValueError("advmil_amd: knn_spatial: |coordinate| must be < 2^30")
+    return c.to(torch.int32).contiguous()
+
+
+def _knn_dev(t, name):
+    if not t.is_cuda:
+        raise RuntimeError(f"advmil_amd: `{name}` lives on {t.device}; the HIP path needs a ROCm device tensor "
+                           "(no CPU fallback in the product path)")
+    return t
+
+
+def knn_spatial(xy, k, seg=None, return_dist=False):
+    """nbr[N, k] int32: for every patch the k nearest other patches of its own bag by squared Euclidean distance of the integer
+    coordinates xy[N, 2], exact (int64), as bag-local ids in ascending (distance, id); with return_dist also dist2[N, k] int64."""
+    N = int(xy.shape[0])
+    _knn_check_bags("knn_spatial", N, k, seg)
+    _knn_dev(xy, "xy")
+    c = knn_coords_int32(xy)
+    nbr = torch.empty(N, k, dtype=torch.int32, device=c.device)
+    d2 = torch.empty(N, k, dtype=torch.int64, device=c.device) if return_dist else None
+    _lib.check(_lib.lib().advmil_knn_spatial(_p(c), N, k, 1 if seg is None else seg.nseg, _p(None if seg is None else seg.ptr),
+                                             N if seg is None else seg.max_len, _p(nbr), _p(d2), _stream()), "knn_spatial")
+    return (nbr, d2) if return_dist else nbr
+
+
+def knn_latent(x, k, seg=None, return_dist=False):
+    """nbr[N, k] int32: for every row of x[N, C] (fp32) the k nearest other rows of its own bag by squared Euclidean distance, as
+    bag-local ids in ascending (distance, id); with return_dist also dist2[N, k] fp32. One fused launch over the bf16x3 operand planes
+    of x (taken from the tensor's `_advmil_planes` when it carries them, else split here; C is zero-padded to a multiple of 32, which
+    changes no distance). The arithmetic is bf16x3 whatever ADVMIL_GEMM_MODE says."""
+    if x.dim() != 2:
+        raise ValueError(f"advmil_amd: knn_latent: features must be [N, C], got {tuple(x.shape)}")
+    N, C = int(x.shape[0]), int(x.shape[1])
+    _knn_check_bags("knn_latent", N, k, seg)
+    _chk(x, "x")
+    pl = planes_of(x)
+    if pl is None or pl.single or C % 32 or pl.hi.stride(1) != 1 or pl.hi.stride() != pl.lo.stride() or pl.hi.stride(0) % 8 or pl.ptrs() & 15:
+        xs = x.detach()
+        if C % 32:
+            xs = torch.nn.functional.pad(xs, (0, (-C) % 32))
+        pl = split_planes(xs.contiguous())
+    Cp = int(pl.hi.shape[1])
+    L = _lib.lib()
+    wsb = L.advmil_knn_latent_workspace_bytes(N, Cp, k)
+    ws = _ws(wsb, x.device)
+    nbr = torch.empty(N, k, dtype=torch.int32, device=x.device)
+    d2 = torch.empty(N, k, dtype=torch.float32, device=x.device) if return_dist else None
+    _lib.check(L.advmil_knn_latent(_p(pl.hi), _p(pl.lo), pl.hi.stride(0), N, Cp, k, 1 if seg is None else seg.nseg,
+                                   _p(None if seg is None else seg.ptr), N if seg is None else seg.max_len, _p(nbr), _p(d2), _p(ws), wsb,
+                                   _stream()), "knn_latent")
+    return (nbr, d2) if return_dist else nbr

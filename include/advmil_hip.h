@@ -783,6 +783,27 @@ int advmil_rank_loss_fwd(const float* pred, const float* t, const float* e, int6
 int advmil_rank_loss_bwd(const float* pred, const float* t, const float* e, int64_t n, float gamma, int l2, int add_weight,
                          const double* state4, const float* gout, float* dpred, advmil_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * WSI graph construction (tools/patchgcn_graph_s2.py:70-90 of the reference, exact instead of HNSW), csrc/knn.hip.
+ * Rows of the slab are partitioned into bags by seg_ptr (nseg + 1 int64 offsets, device; NULL with nseg == 1: one bag of N rows);
+ * max_len = the longest bag, 1 <= max_len <= N. nbr[N, k] (int32): row i = the k nearest rows of i's OWN bag other than i itself, as
+ * BAG-LOCAL ids, ascending by (squared distance, id). Self is excluded by index: a duplicate point at distance 0 is a neighbour.
+ * 1 <= k <= 16, N < 2^31. A bag of <= k rows is memory-safe: the slots it cannot fill hold -1 and, in dist2, the largest finite value
+ * of the type (INT64_MAX / FLT_MAX). dist2[N, k] may be NULL. No atomics, no N x N buffer: results are bit-reproducible and do not
+ * depend on what the outputs or the workspace held. Asynchronous on `stream`, capturable.
+ *
+ * advmil_knn_spatial: xy[N, 2] int32 (8-byte aligned), |coordinate| < 2^30 (the caller's duty); squared distances exact in int64.
+ * advmil_knn_latent: x_hi / x_lo = the bf16x3 operand planes of x[N, C] (advmil_split_planes), row pitch ldx >= C halfwords,
+ *   ldx % 8 == 0, both 16-byte aligned, C % 32 == 0. One fused launch forms S = Xq . Xk^T tile by tile with the three-MFMA bf16x3
+ *   product (whatever advmil_set_gemm_mode says, as the attention core) and ranks key j for query i by n_j - 2 s_ij, n_j = the fp32
+ *   squared norm of row j from the planes (a small first launch, kept in `ws`); dist2 (fp32) = max(0, n_i + n_j - 2 s_ij).
+ *   ws >= advmil_knn_latent_workspace_bytes(N, C, k) = 4 N bytes rounded up to 16 (ADVMIL_EWORKSPACE when shorter). */
+int advmil_knn_spatial(const int32_t* xy, int64_t N, int k, int nseg, const int64_t* seg_ptr, int64_t max_len, int32_t* nbr,
+                       int64_t* dist2, advmil_stream_t stream);
+size_t advmil_knn_latent_workspace_bytes(int64_t N, int64_t C, int k);
+int advmil_knn_latent(const void* x_hi, const void* x_lo, int64_t ldx, int64_t N, int64_t C, int k, int nseg, const int64_t* seg_ptr,
+                      int64_t max_len, int32_t* nbr, float* dist2, void* ws, size_t ws_bytes, advmil_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
