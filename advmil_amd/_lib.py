@@ -238,6 +238,12 @@ SIGNATURES = {
     "advmil_knn_latent_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int]),
     "advmil_knn_latent": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int, c_int, c_void_p, c_int64, c_void_p, c_void_p,
                                   c_void_p, c_size_t, c_void_p]),
+    "advmil_kmeans_assign_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int]),
+    "advmil_kmeans_assign": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int,
+                                     c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "advmil_kmeans_update_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int, c_int]),
+    "advmil_kmeans_update": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_int, c_int, c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
+                                     c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
 }
 
 _lib = None

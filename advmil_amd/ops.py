@@ -3050,3 +3050,154 @@ def knn_latent(x, k, seg=None, return_dist=False):
                                    _p(None if seg is None else seg.ptr), N if seg is None else seg.max_len, _p(nbr), _p(d2), _p(ws), wsb,
                                    _stream()), "knn_latent")
     return (nbr, d2) if return_dist else nbr
+
+
+# ---------------------------------------------------------------------------------------
+# Batched k-means over the rows of a slab (advmil_kmeans_assign / advmil_kmeans_update, csrc/kmeans.hip); advmil_amd/wsicluster.py is
+# the public surface over these two
+# ---------------------------------------------------------------------------------------
+KMEANS_MAX_K = 32
+KMEANS_LDS_ROWS = 37856              # K (C + 8) <= this: a bag's split centres stay in LDS for the whole assign launch
+
+
+def _kmeans_check(what, N, K, seg, min_rows=True):
+    """The checks that need no device: K, the partition, and every bag with at least K rows."""
+    if isinstance(K, bool) or not isinstance(K, int) or not 1 <= K <= KMEANS_MAX_K:
+        raise ValueError(f"advmil_amd: {what}: n_clusters = {K!r}, must be an integer in 1..{KMEANS_MAX_K}")
+    lens = [N] if seg is None else seg.lens
+    if sum(lens) != N:
+        raise ValueError(f"advmil_amd: {what}: the segments cover {sum(lens)} rows, the input has {N}")
+    if min_rows:
+        for b, n in enumerate(lens):
+            if n < K:
+                raise ValueError(f"advmil_amd: {what}: bag {b} has {n} rows, fewer than n_clusters = {K}")
+
+
+def _kmeans_cent(what, cent, K, C, nseg):
+    if cent.dim() == 2:
+        cent = cent.unsqueeze(0)
+    if cent.dim() != 3 or tuple(cent.shape[:2]) != (nseg, K) or int(cent.shape[2]) not in (C, C + (-C) % 32):
+        raise ValueError(f"advmil_amd: {what}: centres must be [{nseg}, {K}, {C}]" + (f" or [{K}, {C}]" if nseg == 1 else "")
+                         + f", got {tuple(cent.shape)}")
+    return cent
+
+
+def _kmeans_i32(what, t, name, n):
+    if t is None:
+        return None
+    if t.dtype != torch.int32 or tuple(t.shape) != (n,) or not t.is_contiguous():
+        raise ValueError(f"advmil_amd: {what}: `{name}` must be a contiguous int32 tensor of {n} elements, got {t.dtype} {tuple(t.shape)}")
+    return _knn_dev(t, name)
+
+
+def kmeans_pad(x):
+    """x[..., C] with C zero-padded to a multiple of 32 (what both k-means kernels take); x itself when nothing is to pad."""
+    C = int(x.shape[-1])
+    return x if C % 32 == 0 else torch.nn.functional.pad(x, (0, (-C) % 32))
+
+
+def kmeans_planes(x):
+    """The bf16x3 operand planes of x[N, C] that kmeans_assign reads: the tensor's own (`_advmil_planes`) when they fit the contract,
+    else a fresh split of the zero-padded rows."""
+    C = int(x.shape[1])
+    pl = planes_of(x)
+    if pl is None or pl.single or C % 32 or pl.hi.stride(1) != 1 or pl.hi.stride() != pl.lo.stride() or pl.hi.stride(0) % 8 or pl.ptrs() & 15:
+        pl = split_planes(kmeans_pad(x.detach()).contiguous())
+    return pl
+
+
+def kmeans_assign(x, cent, seg=None, active=None, labels=None, return_dist=False, return_changed=False, planes=None, norms=None):
+    """labels[N] int32: for every row of x[N, C] (fp32) the nearest of its own bag's K centres cent[nseg, K, C] ([K, C] for one bag),
+    ties to the lowest index; one launch over the bf16x3 operand planes of x (`planes`, else kmeans_planes(x); C is zero-padded to a
+    multiple of 32, which changes no distance), bf16x3 whatever ADVMIL_GEMM_MODE says. `labels` given: updated in place, and with
+    return_changed changed[nseg] int32 counts per bag the rows whose label moved (labels None: all of them). `active[nseg]` int32: rows
+    of a bag with active[b] == 0 keep label and dist2 bits. `norms`: the workspace tensor of an earlier call on the same planes (returned
+    last when return_dist / return_changed ask for a tuple), which spares the row-norm launch.
+    -> labels | (labels[, dist2 fp32][, changed], norms)"""
+    if x.dim() != 2:
+        raise ValueError(f"advmil_amd: kmeans_assign: features must be [N, C], got {tuple(x.shape)}")
+    N, C = int(x.shape[0]), int(x.shape[1])
+    nseg = 1 if seg is None else seg.nseg
+    if not isinstance(cent, torch.Tensor) or cent.dim() not in (2, 3):
+        raise ValueError("advmil_amd: kmeans_assign: centres must be a [K, C] or [nseg, K, C] tensor")
+    K = int(cent.shape[-2])
+    _kmeans_check("kmeans_assign", N, K, seg, min_rows=False)
+    cent = _kmeans_cent("kmeans_assign", cent, K, C, nseg)
+    _chk(x, "x")
+    _chk(cent, "cent")
+    active = _kmeans_i32("kmeans_assign", active, "active", nseg)
+    labels = _kmeans_i32("kmeans_assign", labels, "labels", N)
+    pl = planes if planes is not None else kmeans_planes(x)
+    Cp = int(pl.hi.shape[1])
+    if K * (Cp + 8) > KMEANS_LDS_ROWS:
+        raise ValueError(f"advmil_amd: kmeans_assign: K (C + 8) = {K * (Cp + 8)} exceeds {KMEANS_LDS_ROWS}, the centres of a bag must fit in LDS")
+    cent = kmeans_pad(cent).contiguous()
+    L = _lib.lib()
+    wsb = L.advmil_kmeans_assign_workspace_bytes(N, Cp, K)
+    ready = norms is not None
+    if ready and (norms.dtype != torch.float32 or norms.numel() * 4 < wsb or not norms.is_cuda):
+        raise ValueError("advmil_amd: kmeans_assign: `norms` is not the workspace of an earlier call on these rows")
+    ws = norms if ready else _ws(wsb, x.device)
+    if labels is None:
+        labels = torch.full((N,), -1, dtype=torch.int32, device=x.device)
+    d2 = torch.empty(N, dtype=torch.float32, device=x.device) if return_dist is True else (return_dist if isinstance(return_dist, torch.Tensor) else None)
+    if d2 is not None and (d2.dtype != torch.float32 or tuple(d2.shape) != (N,) or not d2.is_contiguous() or not d2.is_cuda):
+        raise ValueError("advmil_amd: kmeans_assign: a dist2 tensor to update must be contiguous fp32 [N] on the device")
+    chg = torch.empty(nseg, dtype=torch.int32, device=x.device) if return_changed else None
+    _lib.check(L.advmil_kmeans_assign(_p(pl.hi), _p(pl.lo), pl.hi.stride(0), N, Cp, K, nseg, _p(None if seg is None else seg.ptr), _p(active),
+                                      _p(cent), 1 if ready else 0, _p(labels), _p(d2), _p(chg), _p(ws), ws.numel() * 4, _stream()), "kmeans_assign")
+    if d2 is None and chg is None:
+        return labels
+    return tuple([labels] + ([d2] if d2 is not None else []) + ([chg] if chg is not None else []) + [ws])
+
+
+def kmeans_update(x, labels, cent, seg=None, active=None, out=None, count=None):
+    """One centre update: cent_new[nseg, K, C] = per bag and cluster the mean of the rows of x[N, C] (fp32) that carry its label,
+    (float)((double)sum / count) with a fixed-order fp32 sum; a cluster without rows keeps its centre of `cent` and has count 0.
+    `out`: the tensor to write (may be `cent` itself, in place); `count`: an int32 [nseg, K] tensor to update (an inactive bag's counts
+    are not written). x and cent must agree in C (both zero-padded to a multiple of 32 when C is not one).
+    -> (cent_new, count int32 [nseg, K], shift2 fp32 [nseg] = sum_j ||cent_new_j - cent_j||^2; 0 for an inactive bag)"""
+    if x.dim() != 2:
+        raise ValueError(f"advmil_amd: kmeans_update: features must be [N, C], got {tuple(x.shape)}")
+    N, C = int(x.shape[0]), int(x.shape[1])
+    nseg = 1 if seg is None else seg.nseg
+    if not isinstance(cent, torch.Tensor) or cent.dim() not in (2, 3):
+        raise ValueError("advmil_amd: kmeans_update: centres must be a [K, C] or [nseg, K, C] tensor")
+    squeeze = cent.dim() == 2
+    K = int(cent.shape[-2])
+    _kmeans_check("kmeans_update", N, K, seg, min_rows=False)
+    c3 = _kmeans_cent("kmeans_update", cent, K, C, nseg)
+    _chk(x, "x")
+    _chk(c3, "cent")
+    labels = _kmeans_i32("kmeans_update", labels, "labels", N)
+    if labels is None:
+        raise ValueError("advmil_amd: kmeans_update: labels are required")
+    active = _kmeans_i32("kmeans_update", active, "active", nseg)
+    xs = kmeans_pad(x.detach())
+    if xs.stride(1) != 1 or xs.stride(0) % 4 or xs.data_ptr() & 15:
+        xs = xs.contiguous()
+    Cp = int(xs.shape[1])
+    cpad = int(c3.shape[2]) != Cp or not c3.is_contiguous()
+    cin = kmeans_pad(c3).contiguous() if cpad else c3
+    if out is not None:
+        if out.dtype != torch.float32 or tuple(out.shape) != tuple(cin.shape) or not out.is_contiguous() or not out.is_cuda:
+            raise ValueError(f"advmil_amd: kmeans_update: `out` must be contiguous fp32 {tuple(cin.shape)} on the device")
+        cnew = out
+    else:
+        cnew = torch.empty_like(cin)
+    if count is None:
+        count = torch.empty(nseg, K, dtype=torch.int32, device=x.device)
+    elif count.dtype != torch.int32 or tuple(count.shape) != (nseg, K) or not count.is_contiguous() or not count.is_cuda:
+        raise ValueError(f"advmil_amd: kmeans_update: `count` must be contiguous int32 [{nseg}, {K}] on the device")
+    shift2 = torch.empty(nseg, dtype=torch.float32, device=x.device)
+    mlen = N if seg is None else seg.max_len
+    L = _lib.lib()
+    wsb = L.advmil_kmeans_update_workspace_bytes(mlen, Cp, K, nseg)
+    ws = _ws(wsb, x.device)
+    _lib.check(L.advmil_kmeans_update(_p(xs), xs.stride(0), N, Cp, K, nseg, _p(None if seg is None else seg.ptr), mlen, _p(active), _p(labels),
+                                      _p(cin), _p(cnew), _p(count), _p(shift2), _p(ws), ws.numel() * 4, _stream()), "kmeans_update")
+    if out is None:
+        cnew = cnew[:, :, :C] if int(cent.shape[-1]) == C else cnew
+        if squeeze:
+            cnew = cnew[0]
+    return cnew, count, shift2

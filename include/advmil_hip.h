@@ -804,6 +804,37 @@ size_t advmil_knn_latent_workspace_bytes(int64_t N, int64_t C, int k);
 int advmil_knn_latent(const void* x_hi, const void* x_lo, int64_t ldx, int64_t N, int64_t C, int k, int nseg, const int64_t* seg_ptr,
                       int64_t max_len, int32_t* nbr, float* dist2, void* ws, size_t ws_bytes, advmil_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Batched k-means over the rows of a slab (the cluster ids of bcb_mode: cluster; tools/deepattnmisl_cluster.py of the reference runs
+ * sklearn KMeans on the CPU), csrc/kmeans.hip. Conventions of the k-NN entry points above: bags by seg_ptr (NULL with nseg == 1: one
+ * bag), every bag has its own K centres cent[nseg, K, C] (fp32, 16-byte aligned), a row meets its own bag's centres only. No atomics:
+ * bit-reproducible, independent of what outputs and workspace held, and a bag gives the same bits alone and inside a slab.
+ * 1 <= K <= 32, C % 32 == 0, N < 2^31. active[nseg] (int32, device; NULL = every bag): a bag with active[b] == 0 is not touched.
+ * Asynchronous on `stream`.
+ *
+ * advmil_kmeans_assign: x_hi / x_lo = the bf16x3 operand planes of x[N, C], contract of advmil_knn_latent (pitch ldx >= C halfwords,
+ *   ldx % 8 == 0, 16-byte aligned). The centres are split to hi / lo inside the launch and stay in LDS, which bounds
+ *   K (C + 8) <= 37 856 (ADVMIL_EINVAL beyond). S = X . cent^T is the three-MFMA bf16x3 product whatever advmil_set_gemm_mode says;
+ *   centre j is ranked for row i by c_j - 2 s_ij (c_j = fp32 squared norm of the split centre), ties to the lowest j.
+ *   labels[N] (int32) is read AND written: changed[nseg] (may be NULL) = the rows of the bag whose label differs from the value labels
+ *   held on entry, 0 for an inactive bag. dist2[N] (may be NULL) = max(0, n_i + c_j - 2 s_ij), n_i as in advmil_knn_latent.
+ *   ws >= advmil_kmeans_assign_workspace_bytes = the row norms and the rows' moved flags (8 N bytes, each half rounded up to 16);
+ *   norms_ready != 0: ws still holds the norms an earlier call on the same planes left there, the norm launch is skipped.
+ * advmil_kmeans_update: x[N, C] fp32 (row pitch ldx >= C floats, ldx % 4 == 0, 16-byte aligned), labels as written by assign (a row
+ *   whose label is outside [0, K) is skipped), max_len = the longest bag. cent_new[nseg, K, C] (may be cent itself) = per cluster
+ *   (float)((double)sum / count), sum = the fp32 sum over the bag's rows in a fixed order: chunks of 128 rows counted from the BAG's
+ *   first row, in row order inside a chunk, chunks folded in ascending order. A cluster without rows keeps its centre, count 0.
+ *   count[nseg, K] int32; shift2[nseg] = sum_j ||cent_new_j - cent_j||^2. Inactive bag: cent_new = cent bit for bit, shift2 = 0,
+ *   count not written. */
+size_t advmil_kmeans_assign_workspace_bytes(int64_t N, int64_t C, int K);
+int advmil_kmeans_assign(const void* x_hi, const void* x_lo, int64_t ldx, int64_t N, int64_t C, int K, int nseg, const int64_t* seg_ptr,
+                         const int32_t* active, const float* cent, int norms_ready, int32_t* labels, float* dist2, int32_t* changed,
+                         void* ws, size_t ws_bytes, advmil_stream_t stream);
+size_t advmil_kmeans_update_workspace_bytes(int64_t max_len, int64_t C, int K, int nseg);
+int advmil_kmeans_update(const float* x, int64_t ldx, int64_t N, int64_t C, int K, int nseg, const int64_t* seg_ptr, int64_t max_len,
+                         const int32_t* active, const int32_t* labels, const float* cent, float* cent_new, int32_t* count, float* shift2,
+                         void* ws, size_t ws_bytes, advmil_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
