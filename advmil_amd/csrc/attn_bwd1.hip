@@ -525,6 +525,7 @@ extern "C" int advmil_mha_bwd1(const void* qkv_hi, const void* qkv_lo, const flo
   if (!out || !dout || !lse || !dqkv || !ws) return ADVMIL_EINVAL;
   if (((uintptr_t)out & 15) || ((uintptr_t)dout & 15) || ((uintptr_t)dqkv & 15) || ((uintptr_t)ws & 15)) return ADVMIL_EINVAL;
   if (ws_bytes < advmil_mha_bwd1_workspace_bytes(Ltot, nhead, head_dim, max_len)) return ADVMIL_EWORKSPACE;
+  if (nseg > 65535) return ADVMIL_EINVAL;          // the reduce puts the bags on gridDim.y: refused before the first launch
   float* dsum = (float*)ws;
   bf16raw* g_hi = (bf16raw*)((char*)ws + attn_ws_dsum_bytes(Ltot, nhead));
   bf16raw* g_lo = (bf16raw*)((char*)g_hi + attn_ws_plane_bytes(Ltot, nhead, head_dim));

@@ -1827,6 +1827,8 @@ class MhaFn(torch.autograd.Function):
     the kernels."""
 
     last_lse = None          # the log-sum-exp of the forward just run (side channel to ops.mha: the forward memo keeps the eval pass's)
+    keep_dsum = False        # tests: copy D = rowsum(dO * O) [L_total, nhead] out of the backward's workspace (both forms lay it first)
+    last_dsum = None
 
     @staticmethod
     def forward(ctx, qkv, nhead, p, seed, sid, seg, rowoff, planes=None, lse_in=None):
@@ -1877,6 +1879,8 @@ class MhaFn(torch.autograd.Function):
         _lib.check((L.advmil_mha_bwd1 if one else L.advmil_mha_bwd)(
             _p(qhi), _p(qlo), _p(out), _p(dO), _p(lse), Lt, nhead, hd, nseg, _p(ptr), mlen, p, _p(seed if p > 0.0 else None), sid,
             _p(rowoff), _p(dqkv), _p(ws), wsb, _stream()), "mha_bwd1" if one else "mha_bwd")
+        if MhaFn.keep_dsum:
+            MhaFn.last_dsum = ws[:Lt * nhead].view(Lt, nhead).clone()
         _stamp("e", "mha_bwd", (Lt, nhead, hd, nseg), 0.0)
         return dqkv, None, None, None, None, None, None, None, None
 

@@ -185,7 +185,8 @@ int advmil_gemm_f32_tiled(int a_kc, int b_kc, int64_t M, int64_t N, int64_t K, c
  *        c_hi / c_lo plane output produce them; 16-byte aligned, row pitch 3*nhead*head_dim. The kernels stream them into LDS by
  *        LDS-DMA and never see the fp32 values.
  *   out  [Ltot, nhead*head_dim];  lse [Ltot, nhead] = log2-domain log-sum-exp of the scaled scores (opaque to the caller)
- *   Rows are a slab of `nseg` bags, bag b = rows [ptr[b], ptr[b+1]) (device int64; NULL = one bag), max_len = longest bag;
+ *   Rows are a slab of `nseg` bags, bag b = rows [ptr[b], ptr[b+1]) (device int64; NULL = one bag), longest bag <= max_len <= Ltot
+ *   (a cap: it sizes the grids, and workgroups beyond a bag's own tiles return; advmil_mha_bwd1 refuses nseg > 65535);
  *   attention never crosses a bag. Any bag length >= 1 (ragged tails are masked). head_dim in {16, 32, 48, 64}: d_model / 8 heads
  *   of the bcb_dims load_backbone accepts (model/backbone.py:30-33; 384 -> 48 in the shipped config).
  * Dropout on the probabilities (train mode; NULL seed or p == 0 = off): one 32-bit hash per (query, 4 consecutive keys),

@@ -9,6 +9,7 @@ import pytest
 import torch
 
 from advmil_amd import synth
+from tests import attn_ref as AR
 from tests import helpers as H
 
 pytestmark = pytest.mark.gpu
@@ -53,28 +54,14 @@ def relerr(a, b):
 
 
 def ref_attention(qkv, lens, masks=None, HD=HD):
-    """float64: per bag and head softmax(q k^T / sqrt(head_dim)) (* mask) v on the packed [L_total, 3*8*head_dim] rows."""
-    outs, r0 = [], 0
-    D = NH * HD
-    for b, L in enumerate(lens):
-        blk = qkv[r0:r0 + L]
-        q, k, v = (t.reshape(L, NH, HD).transpose(0, 1) for t in blk.split(D, dim=1))
-        pr = torch.softmax(q @ k.transpose(-1, -2) / HD ** 0.5, dim=-1)
-        if masks is not None:
-            pr = pr * masks[b]
-        outs.append((pr @ v).transpose(0, 1).reshape(L, D))
-        r0 += L
-    return torch.cat(outs, dim=0)
+    """float64: per bag and head softmax(q k^T / sqrt(head_dim)) (* mask) v on the packed [L_total, 3*8*head_dim] rows (the oracle
+    of tests/attn_ref.py, which the walk tests share, at this file's 8 heads)."""
+    return AR.ref_attention(qkv, lens, masks, nhead=NH, hd=HD)
 
 
 def host_masks(seed, sid, lens, p, rowoff=None):
-    out, r0 = [], 0
-    for b, L in enumerate(lens):
-        rows = np.arange(L) + r0 + (0 if rowoff is None else int(rowoff[b]))
-        m = np.stack([synth.attn_dropout_keep(seed, sid, rows, NH, h, L, p) for h in range(NH)])
-        out.append(torch.from_numpy(m.astype(np.float64) / (1.0 - p)))
-        r0 += L
-    return out
+    """keep / (1 - p) from the kernels' counter hash (tests/attn_ref.py::host_masks with the nominal scale this file always used)."""
+    return AR.host_masks(seed, sid, lens, p, NH, rowoff=rowoff, scale=1.0 / (1.0 - p))
 
 
 @pytest.mark.parametrize("lens,p", [([32], 0.0), ([70], 0.0), ([210], 0.25), ([512], 0.25), ([128, 64, 200], 0.25),
@@ -164,9 +151,9 @@ def test_attention_dropout_statistics():
     assert abs(synth.attn_dropout_scale(0.25) - 1 / 0.75) < 1e-12
 
 
-def test_mha_forced_rescale_and_large_scores(ops):
+def test_mha_forced_rescale_and_large_scores(ops, bwd_form):
     """Online-softmax rescaling: one key per query block dominates late in the key order, so the running max jumps at a late
-    tile (the rare branch a bounded random input never takes); plus scores of magnitude ~60."""
+    tile (the rare branch a bounded random input never takes); plus scores of magnitude ~60. Both backward forms."""
     L = 384
     qkv = rnd("spike", L, 3 * D, scale=0.3)
     q, k = qkv[:, :D], qkv[:, D:2 * D]

@@ -27,6 +27,7 @@ from advmil_amd import synth
 from tests import helpers as H
 from tests import poison as P
 from tests import test_attention_gpu as TA
+from tests import test_attn_walks_gpu as TAW
 from tests import test_gemm_walks_gpu as TW
 from tests import test_genconv_gpu as TG
 from tests import test_kernels_gpu as TK
@@ -674,6 +675,28 @@ def test_attention_forward_with_the_log_sum_exp_given(ops):
         return o, a.grad, lse
     runs(fn)
     under_ff(TA.test_forward_with_the_log_sum_exp_given_equals_the_plain_forward, ops, hd, lens)
+
+
+ATTN_WALKS = [
+    # a cap above the longest bag: workgroups that return in every main grid and in the reduce grid, partial slabs sized by the cap
+    (TAW.RAISED[0], TAW.body_raised_max_len),
+    # five key blocks under the single-pass form: one unrolled group + remainder in the reduce, every partial slab freshly allocated
+    (next(c for c in TAW.SINGLE_PASS if c.lens == (1025,) and c.hd == 48), lambda ops, c, frm: TAW.run(ops, c, frm)),
+]
+
+
+@pytest.mark.parametrize("case,body", ATTN_WALKS, ids=[TAW.cid(c) for c, _ in ATTN_WALKS])
+def test_attention_walks(ops, case, body):
+    """Two walks of tests/test_attn_walks_gpu.py under the single-pass backward: four runs for the bit comparison (O, lse, the
+    gradients and D), once more through the walk file's own float64 body while the allocations are poisoned."""
+    prev = ops.ATTN_BWD
+    ops.ATTN_BWD = "one"
+    try:
+        assert TAW.facts(case).bags[-1].nkb == (5 if case.max_len is None else 2)
+        runs(lambda: TAW.launch(ops, case))
+        under_ff(body, ops, case, "one")
+    finally:
+        ops.ATTN_BWD = prev
 
 
 def test_in_projection_that_writes_qkv_as_planes_only(ops):

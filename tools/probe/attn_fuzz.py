@@ -68,28 +68,19 @@ for case in range(ncase):
     note = ""
     if (not ok and e_f < 1e-4 and e_b < 5e-5) or os.environ.get("ATTN_FUZZ_MODEL") == str(case):
         # Is a forward deviation beyond 3e-5 the ARITHMETIC's (split-bf16: hi.hi + hi.lo + lo.hi per product, the lo.lo term dropped) or
-        # a kernel's? The same forward in float64 with exactly those terms dropped -- scores from the split q / k, output from the split
-        # P / V. A case whose kernel output follows that model to 1.5e-5 while staying inside the 1e-4 contract is the arithmetic at work
+        # a kernel's? The same forward on the host with exactly those terms dropped -- scores from the split q / k, output from the split
+        # P / V, fp32 sums. A case whose kernel output follows that model to 1.5e-5 while staying inside the 1e-4 contract is the arithmetic at work
         # (large scaled scores: seeds 702 / 705, head_dim 16, |s| up to 5.8 / 7.3) and is accepted, with the three numbers printed.
-        def split(x):
-            hi = x.float().bfloat16().double()
-            lo = (x - hi).float().bfloat16().double()
-            return hi, lo
-        outs, r0, smax = [], 0, 0.0
-        D_ = NH * hd
-        for b, L in enumerate(lens):
-            blk = qkv[r0:r0 + L].double()
-            q_, k_, v_ = (t.reshape(L, NH, hd).transpose(0, 1) for t in blk.split(D_, dim=1))
+        # (tests/attn_ref.py::model: the float32 host model of the kernels' arithmetic, shared with tests/test_attn_walks_gpu.py)
+        from advmil_amd import synth
+        from tests import attn_ref as AR
+        keeps = None if masks is None else [m > 0 for m in masks]
+        om = AR.model(qkv, go, lens, NH, hd, keeps, synth.attn_dropout_scale(p) if p > 0 else 1.0, backward=False)["O"].double()
+        smax, r0 = 0.0, 0
+        for L in lens:
+            q_, k_, _ = AR._heads(qkv[r0:r0 + L].double(), NH, hd)
             smax = max(smax, float((q_ @ k_.transpose(-1, -2)).abs().max() / hd ** 0.5))
-            (qh, ql), (kh, kl), (vh, vl) = split(q_), split(k_), split(v_)
-            s_ = (qh @ kh.transpose(-1, -2) + qh @ kl.transpose(-1, -2) + ql @ kh.transpose(-1, -2)) / hd ** 0.5
-            pr = torch.softmax(s_, dim=-1)
-            if masks is not None:
-                pr = pr * masks[b]
-            ph, pl = split(pr)
-            outs.append((ph @ vh + ph @ vl + pl @ vh).transpose(0, 1).reshape(L, D_))
             r0 += L
-        om = torch.cat(outs, dim=0)
         e_model, e_km = relerr(om, orf), relerr(o, om)
         note = f" [largest |scaled score| {smax:.1f}; split-bf16 model vs float64 {e_model:.2e}; kernel vs the model {e_km:.2e}]"
         if not ok and e_km < 1.5e-5 and bool(torch.isfinite(o).all()) and bool(torch.isfinite(a.grad).all()):
