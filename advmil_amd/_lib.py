@@ -244,6 +244,11 @@ SIGNATURES = {
     "advmil_kmeans_update_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int, c_int]),
     "advmil_kmeans_update": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_int, c_int, c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
                                      c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "advmil_kmeans_seed_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int, c_int]),
+    "advmil_kmeans_seed_cand": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int, c_int, c_void_p, c_int64, c_void_p, c_void_p,
+                                        c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "advmil_kmeans_seed_pick": (c_int, [c_int64, c_int, c_int, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p,
+                                        c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
 }
 
 _lib = None

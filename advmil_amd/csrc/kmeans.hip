@@ -11,6 +11,11 @@
 //   takes a strict-< running minimum of c_j - 2 s_ij, the two lane halves are merged by (rank, j) -> ties go to the lowest j.
 // update: per (bag, chunk of KM_UR rows counted from the bag's first row) the per-cluster column sums in row order, then a fold over
 //   the chunks in ascending order, mean = (float)((double)sum / count); an empty cluster keeps its centre.
+// seeding (sklearn's greedy k-means++, one pick = two launches over the whole slab): the candidate pass forms, with the MFMA product
+//   of assign, the distance of every row to its bag's L trial rows (read from the planes themselves), m_il = min(closest_i, d_il), and
+//   the float64 sum of m_il over every chunk of KM_UR rows of the bag; the pick pass folds the chunks (ascending), keeps the trial with
+//   the lowest potential, makes its m the new closest, scans it in float64 (chunk carry = the fold of the chunks before, so the last
+//   prefix IS the potential) and places the next pick's L draws u * potential in the scan (np.searchsorted side="left", clipped).
 #include <float.h>
 #include "bf16split.h"
 #include "advmil_hip.h"
@@ -355,6 +360,171 @@ __global__ void kmeans_shift_kernel(int K, int nseg, int nct, const int32_t* __r
 }
 
 // ------------------------------------------------------------------------------------------------------------------------------
+// greedy k-means++ seeding
+// ------------------------------------------------------------------------------------------------------------------------------
+#define KM_MAXL 8             // trials per pick (2 + int(ln K) <= 5 at K <= 32): registers 0..3 of the two lane halves hold slots 0..3 | 4..7
+
+// a bag-local row index from device memory, clamped into the bag: no index array can send a read outside [lo, hi)
+__device__ __forceinline__ int64_t km_local_row(int32_t v, int64_t n) { return v < 0 ? 0 : (v >= n ? n - 1 : (int64_t)v); }
+
+// grid (chunk of KM_UR rows counted from the BAG's first row, bag). The bag's L trial rows are copied from the planes into LDS and
+// are the A operand; wave w owns the 32 rows [32 w, 32 w + 32) of the chunk and walks every feature chunk itself, with one
+// accumulator per residue of the chunk index mod 4, summed ((0 + 1) + 2) + 3 -- the partial sums of assign's four waves in assign's
+// order, so d_il has the bits kmeans_assign gives for row i against the centre x[cand_l]. Writes candmin[N, L] and, per (bag, chunk),
+// cpot[bag][chunk][L] = the float64 sum of the chunk's m_il in row order.
+__global__ __launch_bounds__(KM_THREADS) void kmeans_seed_cand_kernel(const bf16raw* __restrict__ xh, const bf16raw* __restrict__ xl, int64_t ldx,
+                                                                       int64_t N, int64_t C, int L, int nseg, const int64_t* __restrict__ seg_ptr,
+                                                                       int mchunk, const int32_t* __restrict__ cand,
+                                                                       const float* __restrict__ closest, const float* __restrict__ norms,
+                                                                       float* __restrict__ candmin, double* __restrict__ cpot) {
+  extern __shared__ __attribute__((aligned(16))) bf16raw km_lds[];         // t_hi [L][C + KM_PAD] | t_lo [L][C + KM_PAD]
+  __shared__ float mlds[KM_UR * KM_MAXL];                                  // m_il of the chunk: [row][L]
+  __shared__ float sc[KM_MAXL];                                            // n of the trial rows
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, r = lane & 31, h = lane >> 5;
+  const int b = blockIdx.y, chunk = blockIdx.x;
+  int64_t lo, hi;
+  km_bag_bounds(seg_ptr, N, b, lo, hi);
+  const int64_t r0 = lo + (int64_t)chunk * KM_UR;
+  if (r0 >= hi) return;                                   // (workgroup-uniform)
+  const int nr = (int)(hi - r0 < KM_UR ? hi - r0 : KM_UR);
+  const int P = (int)C + KM_PAD;
+  bf16raw* ch_ = km_lds;
+  bf16raw* cl_ = km_lds + (size_t)L * P;
+  for (int64_t i8 = tid; i8 < (int64_t)L * (C / 8); i8 += KM_THREADS) {
+    const int j = (int)(i8 / (C / 8)), c = 8 * (int)(i8 % (C / 8));
+    const int64_t cr = lo + km_local_row(cand[(size_t)b * L + j], hi - lo);
+    *(uint4*)(ch_ + j * P + c) = *(const uint4*)(xh + cr * ldx + c);
+    *(uint4*)(cl_ + j * P + c) = *(const uint4*)(xl + cr * ldx + c);
+  }
+  if (tid < L) sc[tid] = norms[lo + km_local_row(cand[(size_t)b * L + tid], hi - lo)];
+  __syncthreads();
+
+  const int64_t qi = r0 + 32 * w + r;
+  const int64_t qr = qi < hi ? qi : hi - 1;               // rows past the bag: a clamped copy, never written
+  const int nch = (int)((C + KM_CH - 1) / KM_CH);
+  const bool half_last = (C % KM_CH) != 0;
+  const int jr = r < L ? r : L - 1;                       // trial slots >= L: a clamped copy, never written
+  if (32 * w < nr) {                                      // (wave-uniform)
+    f32x16 acc[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+#pragma unroll
+      for (int e = 0; e < 16; ++e) acc[k][e] = 0.f;
+    for (int c0 = 0; c0 < nch; c0 += 4) {
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const int c = c0 + k;
+        if (c < nch) {
+          const bool hf = half_last && c == nch - 1;
+          const int co = c * KM_CH + (hf ? 16 : 32) * h;
+          const bf16raw* ph = xh + qr * ldx + co;
+          const bf16raw* pl = xl + qr * ldx + co;
+#pragma unroll
+          for (int s = 0; s < 4; ++s) {
+            if (s < 2 || !hf) {
+              Frag8 ah, al, bh, bl;
+              ah.u = *(const uint4*)(ch_ + jr * P + co + 8 * s);
+              al.u = *(const uint4*)(cl_ + jr * P + co + 8 * s);
+              bh.u = *(const uint4*)(ph + 8 * s);
+              bl.u = *(const uint4*)(pl + 8 * s);
+              acc[k] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al.v, bh.v, acc[k], 0, 0, 0);
+              acc[k] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah.v, bl.v, acc[k], 0, 0, 0);
+              acc[k] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah.v, bh.v, acc[k], 0, 0, 0);
+            }
+          }
+        }
+      }
+    }
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const int j = e + 4 * h;
+      const float s = ((acc[0][e] + acc[1][e]) + acc[2][e]) + acc[3][e];
+      if (j < L && qi < hi) {
+        const float d = fmaxf(0.f, norms[qi] + fmaf(-2.f, s, sc[j]));
+        const float m = closest ? fminf(closest[qi], d) : d;
+        candmin[(size_t)qi * L + j] = m;
+        mlds[(32 * w + r) * L + j] = m;
+      }
+    }
+  }
+  __syncthreads();
+  if (tid < L) {
+    double s = 0.0;
+    for (int k = 0; k < nr; ++k) s += (double)mlds[k * L + tid];
+    cpot[((size_t)b * mchunk + chunk) * L + tid] = s;
+  }
+}
+
+// grid (chunk, bag), KM_UR threads, one row each. Every workgroup folds the bag's chunk potentials itself (ascending; the value before
+// its own chunk is its scan carry), so the launch needs no second pass: pot[b, l], best = the first minimum, row_out[b] = cand[b, best]
+// (from chunk 0), closest_i = candmin[i, best], cum_i = carry + the float64 sum of the chunk's closest up to row i in row order. The
+// last row's cum is the fold of every chunk: the bag's potential. Draw l of the next pick lands on the first row with
+// cum_i >= u_l * potential (the bag's last row when there is none): exactly one row of the bag meets the test, so one thread writes.
+__global__ __launch_bounds__(KM_UR) void kmeans_seed_pick_kernel(int64_t N, int L, int nseg, const int64_t* __restrict__ seg_ptr, int mchunk,
+                                                                 const int32_t* __restrict__ cand, const float* __restrict__ candmin,
+                                                                 const double* __restrict__ cpot, const double* __restrict__ u, int64_t u_stride,
+                                                                 int L_next, int64_t* __restrict__ row_out, int64_t row_stride,
+                                                                 double* __restrict__ pot, float* __restrict__ closest,
+                                                                 int32_t* __restrict__ cand_next) {
+  __shared__ double spot[KM_MAXL], spre[KM_MAXL], dcum[KM_UR];
+  __shared__ float sv[KM_UR];
+  __shared__ int sbest;
+  const int b = blockIdx.y, chunk = blockIdx.x, t = threadIdx.x;
+  int64_t lo, hi;
+  km_bag_bounds(seg_ptr, N, b, lo, hi);
+  const int64_t r0 = lo + (int64_t)chunk * KM_UR;
+  if (r0 >= hi) return;                                   // (workgroup-uniform)
+  const int nr = (int)(hi - r0 < KM_UR ? hi - r0 : KM_UR);
+  int nchunk = (int)((hi - lo + KM_UR - 1) / KM_UR);
+  nchunk = nchunk < mchunk ? nchunk : mchunk;
+  if (t < L) {
+    double s = 0.0, pre = 0.0;
+    for (int c = 0; c < nchunk; ++c) {
+      if (c == chunk) pre = s;
+      s += cpot[((size_t)b * mchunk + c) * L + t];
+    }
+    spot[t] = s;
+    spre[t] = pre;
+    if (chunk == 0) pot[(size_t)b * L + t] = s;
+  }
+  __syncthreads();
+  if (t == 0) {
+    int best = 0;
+    for (int l = 1; l < L; ++l)
+      if (spot[l] < spot[best]) best = l;                 // strict: ties (and NaN) keep the lowest l
+    sbest = best;
+    if (chunk == 0) row_out[(size_t)b * row_stride] = km_local_row(cand[(size_t)b * L + best], hi - lo);
+  }
+  __syncthreads();
+  const int best = sbest;
+  const double total = spot[best], pre = spre[best];
+  const int64_t qi = r0 + t;
+  if (t < nr) {
+    const float v = candmin[(size_t)qi * L + best];
+    closest[qi] = v;
+    sv[t] = v;
+  }
+  if (L_next <= 0) return;                                // (uniform) the last pick draws nothing
+  __syncthreads();
+  if (t == 0) {
+    double s = 0.0;
+    for (int k = 0; k < nr; ++k) {
+      s += (double)sv[k];
+      dcum[k] = pre + s;
+    }
+  }
+  __syncthreads();
+  if (t < nr) {
+    const double cur = dcum[t], prev = t > 0 ? dcum[t - 1] : pre;
+    const bool head = chunk == 0 && t == 0, last = qi == hi - 1;
+    for (int l = 0; l < L_next; ++l) {
+      const double target = u[(size_t)b * u_stride + l] * total;
+      if ((head || !(prev >= target)) && (cur >= target || last)) cand_next[(size_t)b * L_next + l] = (int32_t)(qi - lo);
+    }
+  }
+}
+
+// ------------------------------------------------------------------------------------------------------------------------------
 // host
 // ------------------------------------------------------------------------------------------------------------------------------
 static inline bool km_args_bad(int64_t N, int64_t C, int K, int nseg, const int64_t* seg_ptr) {
@@ -401,6 +571,65 @@ extern "C" int advmil_kmeans_assign(const void* x_hi, const void* x_lo, int64_t 
 }
 
 static inline bool km_len_bad(int64_t N, int64_t max_len) { return max_len <= 0 || max_len > N; }
+
+// the state of a seeding in progress: the rows' squared norms | the chunk potentials [nseg][chunks of KM_UR rows][L] (float64) that the
+// candidate pass leaves for the pick pass
+static inline bool km_seed_bad(int64_t N, int L, int nseg, const int64_t* seg_ptr, int64_t max_len) {
+  return N <= 0 || N >= ((int64_t)1 << 31) || L < 1 || L > KM_MAXL || nseg < 1 || nseg > 65535 || (nseg > 1 && !seg_ptr) || km_len_bad(N, max_len);
+}
+extern "C" size_t advmil_kmeans_seed_workspace_bytes(int64_t N, int64_t max_len, int L, int nseg) {
+  if (N <= 0 || max_len <= 0 || L < 1 || L > KM_MAXL || nseg < 1) return 0;
+  return km_up16((size_t)N * 4) + km_up16((size_t)nseg * (size_t)((max_len + KM_UR - 1) / KM_UR) * L * 8);
+}
+
+extern "C" int advmil_kmeans_seed_cand(const void* x_hi, const void* x_lo, int64_t ldx, int64_t N, int64_t C, int L, int nseg,
+                                       const int64_t* seg_ptr, int64_t max_len, const int32_t* cand, const float* closest, int norms_ready,
+                                       float* candmin, void* ws, size_t ws_bytes, advmil_stream_t stream) {
+  if (!x_hi || !x_lo || !cand || !candmin || C <= 0 || C % 32 || km_seed_bad(N, L, nseg, seg_ptr, max_len)) return ADVMIL_EINVAL;
+  if (ldx < C || ldx % 8 || (((uintptr_t)x_hi | (uintptr_t)x_lo) & 15) || (((uintptr_t)cand | (uintptr_t)candmin | (uintptr_t)closest) & 3))
+    return ADVMIL_EINVAL;
+  const size_t lds = (size_t)2 * L * (C + KM_PAD) * sizeof(bf16raw);
+  const size_t fixed = (KM_UR * KM_MAXL + KM_MAXL) * sizeof(float);
+  if (lds + fixed > KM_LDS_MAX) return ADVMIL_EINVAL;                      // the bag's trial rows stay in LDS
+  if (ws_bytes < advmil_kmeans_seed_workspace_bytes(N, max_len, L, nseg)) return ADVMIL_EWORKSPACE;
+  if (!ws || ((uintptr_t)ws & 15)) return ADVMIL_EINVAL;
+  static const int attr = (int)hipFuncSetAttribute(reinterpret_cast<const void*>(kmeans_seed_cand_kernel),
+                                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)(KM_LDS_MAX - fixed));
+  if (attr != 0) return attr;
+  float* norms = (float*)ws;
+  double* cpot = (double*)((char*)ws + km_up16((size_t)N * 4));
+  const int m = (int)((max_len + KM_UR - 1) / KM_UR);
+  if (!norms_ready) {
+    hipLaunchKernelGGL(kmeans_norms_kernel, dim3((unsigned)((N + 3) / 4)), dim3(KM_THREADS), 0, (hipStream_t)stream, (const bf16raw*)x_hi,
+                       (const bf16raw*)x_lo, ldx, N, C, norms);
+    ADVMIL_LAUNCH_CHECK();
+  }
+  hipLaunchKernelGGL(kmeans_seed_cand_kernel, dim3((unsigned)m, (unsigned)nseg), dim3(KM_THREADS), lds, (hipStream_t)stream,
+                     (const bf16raw*)x_hi, (const bf16raw*)x_lo, ldx, N, C, L, nseg, seg_ptr, m, cand, closest, (const float*)norms, candmin,
+                     cpot);
+  ADVMIL_LAUNCH_CHECK();
+  return ADVMIL_OK;
+}
+
+extern "C" int advmil_kmeans_seed_pick(int64_t N, int L, int nseg, const int64_t* seg_ptr, int64_t max_len, const int32_t* cand,
+                                       const float* candmin, const double* u, int64_t u_stride, int L_next, int64_t* row_out,
+                                       int64_t row_stride, double* pot, float* closest, int32_t* cand_next, const void* ws, size_t ws_bytes,
+                                       advmil_stream_t stream) {
+  if (!cand || !candmin || !row_out || !pot || !closest || km_seed_bad(N, L, nseg, seg_ptr, max_len)) return ADVMIL_EINVAL;
+  if (L_next < 0 || L_next > KM_MAXL || row_stride < 1) return ADVMIL_EINVAL;
+  if (L_next > 0 && (!u || !cand_next || cand_next == cand || u_stride < L_next)) return ADVMIL_EINVAL;
+  if ((((uintptr_t)cand | (uintptr_t)candmin | (uintptr_t)closest | (uintptr_t)cand_next) & 3) ||
+      (((uintptr_t)u | (uintptr_t)row_out | (uintptr_t)pot) & 7))
+    return ADVMIL_EINVAL;
+  if (ws_bytes < advmil_kmeans_seed_workspace_bytes(N, max_len, L, nseg)) return ADVMIL_EWORKSPACE;
+  if (!ws || ((uintptr_t)ws & 15)) return ADVMIL_EINVAL;
+  const double* cpot = (const double*)((const char*)ws + km_up16((size_t)N * 4));
+  const int m = (int)((max_len + KM_UR - 1) / KM_UR);
+  hipLaunchKernelGGL(kmeans_seed_pick_kernel, dim3((unsigned)m, (unsigned)nseg), dim3(KM_UR), 0, (hipStream_t)stream, N, L, nseg, seg_ptr, m,
+                     cand, candmin, cpot, u, u_stride, L_next, row_out, row_stride, pot, closest, cand_next);
+  ADVMIL_LAUNCH_CHECK();
+  return ADVMIL_OK;
+}
 
 extern "C" size_t advmil_kmeans_update_workspace_bytes(int64_t max_len, int64_t C, int K, int nseg) {
   if (max_len <= 0 || C <= 0 || K < 1 || K > KM_MAXK || nseg < 1) return 0;

@@ -19,6 +19,8 @@ Every rank must take the same path, so the choice is agreed on with an all-reduc
 sends all ranks back to the segments, and bench.py runs its multi-rank legs under a stall watchdog. Exercised on this image with a
 one-rank RCCL communicator only (tests/test_parallel_gpu.py); the default stays the segment path until a node has run it.
 """
+import contextlib
+import gc
 import os
 
 import torch
@@ -28,6 +30,22 @@ from . import ops
 
 # the two gradient-arena fills of a step folded into the Adam launches (ADVMIL_CLEAR_IN_ADAM=0: separate fill launches, for A/B timing)
 CLEAR_IN_ADAM = os.environ.get("ADVMIL_CLEAR_IN_ADAM", "1") != "0"
+
+
+@contextlib.contextmanager
+def _gc_paused():
+    """No cyclic garbage collection while a stream captures. A collection that falls inside a capture frees whatever dead cycles have
+    piled up -- an earlier GraphedStep and its handler refer to each other, so only the collector frees them and their
+    torch.cuda.CUDAGraph objects --, and destroying a graph is not a capturable act: on ROCm its destructor synchronises the device,
+    which a capturing thread may not do, and an error raised in a destructor ends the process. The cycles are collected after the
+    capture instead."""
+    on = gc.isenabled()
+    gc.disable()
+    try:
+        yield
+    finally:
+        if on:
+            gc.enable()
 
 
 class GraphedStep:
@@ -147,7 +165,7 @@ class GraphedStep:
             ok = True
             try:
                 g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g, pool=pool, capture_error_mode="thread_local"):
+                with _gc_paused(), torch.cuda.graph(g, pool=pool, capture_error_mode="thread_local"):
                     self._whole()
             except Exception:
                 ok = False
@@ -166,7 +184,7 @@ class GraphedStep:
             for fn in parts:
                 g = torch.cuda.CUDAGraph()
                 # thread_local: RCCL's watchdog thread may query events while this thread captures
-                with torch.cuda.graph(g, pool=pool, capture_error_mode="thread_local"):
+                with _gc_paused(), torch.cuda.graph(g, pool=pool, capture_error_mode="thread_local"):
                     fn()
                 self.segments.append(g)
 

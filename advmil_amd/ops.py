@@ -3205,3 +3205,135 @@ def kmeans_update(x, labels, cent, seg=None, active=None, out=None, count=None):
         if squeeze:
             cnew = cnew[0]
     return cnew, count, shift2
+
+
+# ---------------------------------------------------------------------------------------
+# Greedy k-means++ seeding (advmil_kmeans_seed_cand / advmil_kmeans_seed_pick, csrc/kmeans.hip): sklearn's _kmeans_plusplus for every
+# bag of a slab at once, two launches per pick; advmil_amd/wsicluster.py (seed_rows_greedy) feeds it sklearn's RNG stream
+# ---------------------------------------------------------------------------------------
+KMEANS_SEED_MAX_L = 8
+KMEANS_SEED_LDS_ROWS = 39928         # L (C + 8) <= this: a bag's trial rows stay in LDS for the candidate launch
+
+
+def kmeans_seed_trials(K):
+    """sklearn's n_local_trials = 2 + int(ln K): 2 at K = 1..2, 3 at 3..7, 4 at 8..20, 5 at 21..32."""
+    import math
+    return 2 + int(math.log(K))
+
+
+def _kmeans_seed_t(what, t, name, dtype, shape, dev=True):
+    if not isinstance(t, torch.Tensor) or t.dtype != dtype or tuple(t.shape) != tuple(shape) or not t.is_contiguous():
+        got = f"{t.dtype} {tuple(t.shape)}" if isinstance(t, torch.Tensor) else type(t).__name__
+        raise ValueError(f"advmil_amd: {what}: `{name}` must be a contiguous {dtype} tensor of shape {tuple(shape)}, got {got}")
+    return _knn_dev(t, name) if dev else t
+
+
+def _kmeans_seed_bags(what, N, seg):
+    lens = [N] if seg is None else seg.lens
+    if sum(lens) != N:
+        raise ValueError(f"advmil_amd: {what}: the segments cover {sum(lens)} rows, the input has {N}")
+    if min(lens) < 1:
+        raise ValueError(f"advmil_amd: {what}: an empty bag")
+    return len(lens), max(lens)
+
+
+def kmeans_seed_cand(x, cand, closest=None, seg=None, planes=None, ws=None, out=None):
+    """The candidate pass of one pick: candmin[N, L] fp32 = min(closest_i, d_il), d_il = the squared distance of row i of x[N, C] to
+    row cand[b, l] (int32 [nseg, L], bag-local) of its own bag b, with the bits kmeans_assign gives for that row as a centre;
+    closest None = +inf. The chunk potentials stay in the workspace for kmeans_seed_pick. `ws`: the workspace an earlier call on these
+    rows returned (its norms are reused); `out`: a [N, L] tensor to write. -> (candmin, ws)"""
+    if x.dim() != 2:
+        raise ValueError(f"advmil_amd: kmeans_seed_cand: features must be [N, C], got {tuple(x.shape)}")
+    N = int(x.shape[0])
+    nseg, mlen = _kmeans_seed_bags("kmeans_seed_cand", N, seg)
+    if not isinstance(cand, torch.Tensor) or cand.dim() != 2 or not 1 <= int(cand.shape[1]) <= KMEANS_SEED_MAX_L:
+        raise ValueError(f"advmil_amd: kmeans_seed_cand: `cand` must be int32 [{nseg}, L] with 1 <= L <= {KMEANS_SEED_MAX_L}")
+    Lc = int(cand.shape[1])
+    _kmeans_seed_t("kmeans_seed_cand", cand, "cand", torch.int32, (nseg, Lc))
+    if closest is not None:
+        _kmeans_seed_t("kmeans_seed_cand", closest, "closest", torch.float32, (N,))
+    _chk(x, "x")
+    pl = planes if planes is not None else kmeans_planes(x)
+    Cp = int(pl.hi.shape[1])
+    if Lc * (Cp + 8) > KMEANS_SEED_LDS_ROWS:
+        raise ValueError(f"advmil_amd: kmeans_seed_cand: L (C + 8) = {Lc * (Cp + 8)} exceeds {KMEANS_SEED_LDS_ROWS}, the trial rows of a bag must fit in LDS")
+    L = _lib.lib()
+    wsb = L.advmil_kmeans_seed_workspace_bytes(N, mlen, KMEANS_SEED_MAX_L, nseg)
+    ready = ws is not None
+    if ready and (ws.dtype != torch.float32 or ws.numel() * 4 < wsb or not ws.is_cuda):
+        raise ValueError("advmil_amd: kmeans_seed_cand: `ws` is not the workspace of an earlier call on these rows")
+    ws = ws if ready else _ws(wsb, x.device)
+    candmin = torch.empty(N, Lc, dtype=torch.float32, device=x.device) if out is None else _kmeans_seed_t("kmeans_seed_cand", out, "out", torch.float32, (N, Lc))
+    _lib.check(L.advmil_kmeans_seed_cand(_p(pl.hi), _p(pl.lo), pl.hi.stride(0), N, Cp, Lc, nseg, _p(None if seg is None else seg.ptr), mlen,
+                                         _p(cand), _p(closest), 1 if ready else 0, _p(candmin), _p(ws), ws.numel() * 4, _stream()),
+               "kmeans_seed_cand")
+    return candmin, ws
+
+
+def kmeans_seed_pick(cand, candmin, ws, closest, rows_out, u=None, seg=None, pot=None, cand_next=None):
+    """The pick pass that follows kmeans_seed_cand(…, cand, …) -> (candmin, ws): per bag the trial with the lowest potential
+    (pot[nseg, L] float64, first minimum) goes to rows_out[nseg] (int64, may be a strided column), its candmin column becomes
+    closest[N] (written in place), and with u[nseg, L_next] (float64, may be a strided slice) the next pick's trial rows
+    cand_next[nseg, L_next] int32 are drawn: the first row whose float64 prefix sum of closest reaches u * potential.
+    -> (pot, cand_next or None)"""
+    N, Lc = int(candmin.shape[0]), int(candmin.shape[1])
+    nseg, mlen = _kmeans_seed_bags("kmeans_seed_pick", N, seg)
+    _kmeans_seed_t("kmeans_seed_pick", cand, "cand", torch.int32, (nseg, Lc))
+    _kmeans_seed_t("kmeans_seed_pick", candmin, "candmin", torch.float32, (N, Lc))
+    _kmeans_seed_t("kmeans_seed_pick", closest, "closest", torch.float32, (N,))
+    if not isinstance(rows_out, torch.Tensor) or rows_out.dtype != torch.int64 or tuple(rows_out.shape) != (nseg,) or not rows_out.is_cuda:
+        raise ValueError(f"advmil_amd: kmeans_seed_pick: `rows_out` must be an int64 device tensor of {nseg} elements")
+    Ln = 0
+    if u is not None:
+        if not isinstance(u, torch.Tensor) or u.dtype != torch.float64 or u.dim() != 2 or int(u.shape[0]) != nseg or u.stride(1) != 1 \
+                or not 1 <= int(u.shape[1]) <= KMEANS_SEED_MAX_L or not u.is_cuda:
+            raise ValueError(f"advmil_amd: kmeans_seed_pick: `u` must be a float64 device tensor [{nseg}, L_next] with unit column stride")
+        Ln = int(u.shape[1])
+        cand_next = torch.empty(nseg, Ln, dtype=torch.int32, device=candmin.device) if cand_next is None else \
+            _kmeans_seed_t("kmeans_seed_pick", cand_next, "cand_next", torch.int32, (nseg, Ln))
+    pot = torch.empty(nseg, Lc, dtype=torch.float64, device=candmin.device) if pot is None else \
+        _kmeans_seed_t("kmeans_seed_pick", pot, "pot", torch.float64, (nseg, Lc))
+    L = _lib.lib()
+    if not isinstance(ws, torch.Tensor) or ws.dtype != torch.float32 or not ws.is_cuda \
+            or ws.numel() * 4 < L.advmil_kmeans_seed_workspace_bytes(N, mlen, KMEANS_SEED_MAX_L, nseg):
+        raise ValueError("advmil_amd: kmeans_seed_pick: `ws` is not the workspace kmeans_seed_cand returned for these rows")
+    _lib.check(L.advmil_kmeans_seed_pick(N, Lc, nseg, _p(None if seg is None else seg.ptr), mlen, _p(cand), _p(candmin), _p(u),
+                                         int(u.stride(0)) if Ln and nseg > 1 else max(Ln, 1), Ln, _p(rows_out),
+                                         int(rows_out.stride(0)) if nseg > 1 else 1, _p(pot), _p(closest), _p(cand_next if Ln else None), _p(ws),
+                                         ws.numel() * 4, _stream()), "kmeans_seed_pick")
+    return pot, (cand_next if Ln else None)
+
+
+def kmeans_seed_greedy(x, K, first, u, seg=None, planes=None, return_trace=False):
+    """sklearn's greedy k-means++ for every bag of x[N, C] (fp32) at once -> rows[nseg, K] int64 (bag-local, device).
+    first[nseg] int32 (device): the first centre of each bag; u[nseg, K - 1, L] float64 (device), L = kmeans_seed_trials(K): the
+    uniforms of picks 1..K - 1. 1 + 2 K launches whatever nseg and N are, nothing is read back (capturable on one stream).
+    With return_trace also dict(closest fp32 [N], pot0 [nseg, 1], pot [K - 1, nseg, L] float64, cand int32 [K - 1, nseg, L])."""
+    if x.dim() != 2:
+        raise ValueError(f"advmil_amd: kmeans_seed_greedy: features must be [N, C], got {tuple(x.shape)}")
+    N = int(x.shape[0])
+    _kmeans_check("kmeans_seed_greedy", N, K, seg)
+    nseg = 1 if seg is None else seg.nseg
+    Lt = kmeans_seed_trials(K)
+    _kmeans_seed_t("kmeans_seed_greedy", first, "first", torch.int32, (nseg,), dev=False)      # shapes first: they need no device
+    _kmeans_seed_t("kmeans_seed_greedy", u, "u", torch.float64, (nseg, K - 1, Lt), dev=False)
+    _chk(x, "x")
+    _knn_dev(first, "first")
+    _knn_dev(u, "u")
+    dev = x.device
+    pl = planes if planes is not None else kmeans_planes(x)
+    rows = torch.empty(nseg, K, dtype=torch.int64, device=dev)
+    closest = torch.empty(N, dtype=torch.float32, device=dev)
+    buf = torch.empty(N * Lt, dtype=torch.float32, device=dev)
+    pot0 = torch.empty(nseg, 1, dtype=torch.float64, device=dev)
+    pots = torch.empty(max(K - 1, 1), nseg, Lt, dtype=torch.float64, device=dev)
+    cands = torch.empty(max(K - 1, 1), nseg, Lt, dtype=torch.int32, device=dev)
+    ws = None
+    for p in range(K):
+        cand = first.view(nseg, 1) if p == 0 else cands[p - 1]
+        candmin, ws = kmeans_seed_cand(x, cand, None if p == 0 else closest, seg, pl, ws, out=buf[:N * int(cand.shape[1])].view(N, -1))
+        kmeans_seed_pick(cand, candmin, ws, closest, rows[:, p], u[:, p] if p < K - 1 else None, seg, pot0 if p == 0 else pots[p - 1],
+                         cands[p] if p < K - 1 else None)
+    if not return_trace:
+        return rows
+    return rows, dict(closest=closest, pot0=pot0, pot=pots[:K - 1], cand=cands[:K - 1])

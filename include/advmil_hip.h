@@ -836,6 +836,35 @@ int advmil_kmeans_update(const float* x, int64_t ldx, int64_t N, int64_t C, int 
                          const int32_t* active, const int32_t* labels, const float* cent, float* cent_new, int32_t* count, float* shift2,
                          void* ws, size_t ws_bytes, advmil_stream_t stream);
 
+/* Greedy k-means++ seeding (sklearn's _kmeans_plusplus: every pick tries L = 2 + int(ln K) rows drawn from the D^2 distribution and
+ * keeps the one that lowers the potential most), for every bag of the slab at once: one pick = advmil_kmeans_seed_cand, then
+ * advmil_kmeans_seed_pick, ONE launch each whatever nseg and N are, nothing read back. Conventions of the entry points above (bags by
+ * seg_ptr, max_len = the longest bag, nseg <= 65535, no atomics, a bag gives the same bits alone and inside a slab, asynchronous on
+ * `stream`); 1 <= L <= 8. `ws` >= advmil_kmeans_seed_workspace_bytes(N, max_len, L, nseg) carries the state of the seeding from call
+ * to call: the row norms (4 N bytes rounded up to 16) | the chunk potentials [nseg][ceil(max_len / 128)][L] float64. A workspace sized
+ * for a larger L serves a smaller one.
+ *
+ * advmil_kmeans_seed_cand: planes as advmil_kmeans_assign. cand[nseg, L] (int32) = the bag-local rows on trial (an index outside its
+ *   bag is clamped into it); the trial rows are read from the planes themselves. closest[N] fp32, NULL = +inf (the first centre: L = 1).
+ *   d_il = max(0, n_i + n_cand - 2 s_il) with the bits advmil_kmeans_assign gives for the centre x[cand_l]; writes
+ *   candmin[N, L] = min(closest_i, d_il) and, into ws, the float64 sum of candmin[:, l] over every chunk of 128 rows counted from the
+ *   bag's first row, in row order. 2 L (C + 8) halfwords of LDS: ADVMIL_EINVAL where that exceeds the CU's. norms_ready as in assign.
+ * advmil_kmeans_seed_pick: reads cand, candmin and ws as the candidate pass with the same (N, L, nseg, seg_ptr, max_len) left them.
+ *   pot[nseg, L] (float64) = the chunk sums folded in ascending order; best = the first minimum of pot[b, :] (np.argmin);
+ *   row_out[b * row_stride] (int64) = cand[b, best]; closest_i = candmin[i, best]. With L_next > 0 also the next pick's draws:
+ *   cum = the float64 inclusive prefix sum of closest over the bag (the chunks before a row folded in ascending order, then row order
+ *   inside its chunk; the last prefix equals pot[b, best] bit for bit), cand_next[b, l] = the first row with
+ *   cum_i >= u[b * u_stride + l] * cum_last, the bag's last row when there is none (np.searchsorted side="left", clipped): a bag whose
+ *   potential is 0 yields row 0. u float64 on the device, u_stride >= L_next doubles; cand_next[nseg, L_next] must not be cand.
+ *   L_next == 0 (the last pick): u and cand_next are not read. */
+size_t advmil_kmeans_seed_workspace_bytes(int64_t N, int64_t max_len, int L, int nseg);
+int advmil_kmeans_seed_cand(const void* x_hi, const void* x_lo, int64_t ldx, int64_t N, int64_t C, int L, int nseg, const int64_t* seg_ptr,
+                            int64_t max_len, const int32_t* cand, const float* closest, int norms_ready, float* candmin, void* ws,
+                            size_t ws_bytes, advmil_stream_t stream);
+int advmil_kmeans_seed_pick(int64_t N, int L, int nseg, const int64_t* seg_ptr, int64_t max_len, const int32_t* cand, const float* candmin,
+                            const double* u, int64_t u_stride, int L_next, int64_t* row_out, int64_t row_stride, double* pot,
+                            float* closest, int32_t* cand_next, const void* ws, size_t ws_bytes, advmil_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
