@@ -83,6 +83,11 @@ class Optim(ctypes.Structure):
 
 OPT_KINDS = {"adam": 0, "adamw": 1, "nadam": 2, "radam": 3, "adadelta": 4}       # ADVMIL_OPT_*
 
+# advmil_cindex_counts_weighted (csrc/evalk.hip: CB_T, CB_R, CB_MAX_CHUNK_BLOCKS; advmil_cindex_counts_weighted_plan answers the same)
+CINDEX_BOOT_ROW_TILE = 256               # threads of a workgroup = stride of its walk over the samples
+CINDEX_BOOT_RESAMPLE_CHUNK = 8           # resamples a workgroup carries in registers
+CINDEX_BOOT_MAX_CHUNK_BLOCKS = 4096      # more chunks than this: a workgroup takes several, CINDEX_BOOT_MAX_CHUNK_BLOCKS apart
+
 
 # name -> (restype, argtypes); must list every symbol include/advmil_hip.h declares
 SIGNATURES = {
@@ -222,6 +227,9 @@ SIGNATURES = {
     "advmil_flush_sums": (c_int, [c_void_p]),
     "advmil_pending_sums": (c_int, [c_void_p]),
     "advmil_cindex_counts": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_float, c_void_p, c_void_p]),
+    "advmil_cindex_counts_weighted": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_int64, c_int, c_int64, c_float,
+                                              c_void_p, c_void_p]),
+    "advmil_cindex_counts_weighted_plan": (c_int, [ctypes.POINTER(c_int), ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),
     "advmil_surv_metrics_cont_workspace_bytes": (c_size_t, [c_int64]),
     "advmil_surv_metrics_cont": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_float, c_float, c_int, c_float, c_int, c_void_p,
                                          c_void_p, c_size_t, c_void_p]),

@@ -744,6 +744,23 @@ int advmil_mask_rows(const float* x, const float* mask, int64_t B, int64_t K, fl
 int advmil_cindex_counts(const float* time, const float* event, const float* estimate, int64_t n, float tied_tol, int64_t* out6,
                          advmil_stream_t stream);
 
+/* The same counts for B weighted resamples and M estimate rows at once (bootstrap of the concordance index). weights[B, ldw] (device,
+ * int32, every entry >= 0): weights[b, i] = how often sample i occurs in resample b. estimate[M, lde]; lde, ldw >= n (elements).
+ * out[M, B, 8] (device, int64): out[m, b, 0..5] is exactly what advmil_cindex_counts writes for the arrays in which sample i stands
+ * weights[b, i] times (in any order) with estimate row m; out[m, b, 6] = sum_i w_i [event_i != 0] (event copies), out[m, b, 7] =
+ * sum_i w_i (size of the resample). Per event anchor i with w_i > 0 and per j: the pair is comparable iff t_j > t_i, or t_j == t_i and
+ * event_j == 0; each counter of the pair grows by w_i * w_j; events_with_entry += w_i * [sum_j w_j [t_j >= t_i] - 1 > 0] (j == i
+ * included: copies of one sample are never comparable with each other, but they are entries of each other). Integer arithmetic in
+ * 64-bit counters throughout (integer atomicAdd into `out`, which the call clears first): bit-identical from run to run and
+ * independent of what `out` held; no workspace. 1 <= n, B <= 2^20, 1 <= M <= 64, tied_tol >= 0, weights / estimate 4-byte and out
+ * 8-byte aligned, else ADVMIL_EINVAL before anything is enqueued. Asynchronous on `stream`, capturable.
+ * advmil_cindex_counts_weighted_plan: the kernel's constants (pure host function): threads striding over j, resamples per chunk,
+ * and the number of chunks beyond which one workgroup takes several. */
+int advmil_cindex_counts_weighted(const float* time, const float* event, const float* estimate, int64_t lde, int M,
+                                  const int32_t* weights, int64_t ldw, int B, int64_t n, float tied_tol, int64_t* out,
+                                  advmil_stream_t stream);
+int advmil_cindex_counts_weighted_plan(int* row_tile, int* resample_chunk, int* max_chunk_blocks);
+
 /* ------------------------------------------------------------------------------------------
  * Survival evaluators (eval/evaluator.py:11,133,213) and the two O(n^2) pair losses (loss/utils.py:43-80, 155-175), csrc/survk.hip.
  * fp32 inputs; every term is formed in fp32 (exp / log of a term: the hardware v_exp_f32 / v_log_f32, ~1 ulp), every sum is carried
