@@ -1,5 +1,7 @@
 from .cindex import concordance_index, concordance_index_censored, NoComparablePairException  # noqa: F401
 from .bootstrap import (bootstrap_concordance_index, bootstrap_concordance_samples, concordance_counts_weighted,  # noqa: F401
                         multiplicities, paired_bootstrap_concordance, resample_indices)
+from .stratify import (kaplan_meier, logrank_from_rows, logrank_permutation_test, logrank_rows, logrank_scan, logrank_test,  # noqa: F401
+                       permutation_groups, risk_groups, stratify)
 from .evaluator import ContSurv_Evaluator, DiscSurv_Evaluator, CoxSurv_Evaluator  # noqa: F401
 from .utils import prepare_evaluator  # noqa: F401

@@ -19,6 +19,7 @@ from .. import _lib
 from ..loss import utils as LU
 from .bootstrap import bootstrap_concordance_index, bootstrap_risk
 from .cindex import concordance_index, concordance_index_censored
+from .stratify import _risks, stratify_risk
 
 _WHICH = {"bce": 0, "hinge": 1, "wasserstein": 2}
 # slots of the result array (doubles): [0, 16) the family's fused sums, [16, 20) rank_loss state, [20, 22) SurvPLE
@@ -108,6 +109,23 @@ class _Evaluator(object):
         defined C-index (more than 5 % of them: ValueError)."""
         b = self._bootstrap_c_index(data, n_boot, seed, level)
         return {"c_index": b.cindex, "c_index_lo": b.lo, "c_index_hi": b.hi, "c_index_se": b.se, "n_undefined": b.n_undefined}
+
+    def _risk_estimate(self, data):
+        """-> (event, time, risk) on the device: the estimate vector `_bootstrap_c_index` hands to the bootstrap."""
+        dev = _device_of(data)
+        y = _f32(data["y"], dev)
+        pred = _f32(data["avg_y_hat"] if "avg_y_hat" in data else data["y_hat"], dev).reshape(-1)
+        return _risks(y, pred.reshape(-1, 1))[:3]
+
+    def stratify(self, data, q=0.5, n_perm=0, n_boot=0, seed=0, level=0.95):
+        """Split the cohort at the `q`-quantile of the risk the `c_index` metric ranks by and compare the two groups (eval/stratify.py,
+        one launch): group sizes and events, Kaplan-Meier medians, the log-rank z, chi2 and p, with `n_perm` > 0 the permutation p-value
+        and with `n_boot` > 0 the bootstrap interval of z and how many resamples had no statistic (more than 5 % of them: ValueError)."""
+        e, t, risk = self._risk_estimate(data)
+        s = stratify_risk(e, t, risk, q=q, n_perm=n_perm, n_boot=n_boot, seed=seed, level=level)
+        return {"n_low": s.n_low, "n_high": s.n_high, "events_low": s.events_low, "events_high": s.events_high, "median_low": s.median_low,
+                "median_high": s.median_high, "z": s.z, "chi2": s.chi2, "p": s.p, "p_perm": s.p_perm, "z_lo": s.z_lo, "z_hi": s.z_hi,
+                "n_undefined": s.n_undefined}
 
 
 class ContSurv_Evaluator(_Evaluator):
@@ -258,6 +276,26 @@ class DiscSurv_Evaluator(_Evaluator):
         _lib.check(L.advmil_surv_metrics_disc(_p(hz), hz.stride(0), _p(t), _p(e), None, n, bins, 0.0, 1e-7, 0, _p(risk), _p(res), _p(ws), wsb,
                                               _stream(dev)), "surv_metrics_disc")
         return bootstrap_risk(e, t, -risk, n_boot=n_boot, seed=seed, level=level)
+
+    def _risk_estimate(self, data):
+        dev = _device_of(data)
+        y = _f32(data["y"], dev)
+        t, e = y[:, 0].contiguous(), y[:, 1].contiguous()
+        hz = _f32(data["avg_y_hat"] if "avg_y_hat" in data else data["y_hat"], dev)
+        hz = hz.reshape(hz.shape[0], -1)
+        n, bins = hz.shape
+        if bins == 1:
+            return _risks(y, hz)[:3]
+        if bins > 256:
+            raise ValueError(f"DiscSurv_Evaluator: {bins} bins; the HIP path takes 1 to 256")
+        L = _lib.lib()
+        res = torch.empty(_NRES, dtype=torch.float64, device=dev)
+        risk = torch.empty(n, dtype=torch.float32, device=dev)    # the fused pass's risk: the bits `compute` ranks by
+        wsb = L.advmil_surv_metrics_disc_workspace_bytes(n)
+        ws = _ws(wsb, dev)
+        _lib.check(L.advmil_surv_metrics_disc(_p(hz), hz.stride(0), _p(t), _p(e), None, n, bins, 0.0, 1e-7, 0, _p(risk), _p(res), _p(ws), wsb,
+                                              _stream(dev)), "surv_metrics_disc")
+        return e, t, -risk
 
 
 class CoxSurv_Evaluator(_Evaluator):

@@ -762,6 +762,33 @@ int advmil_cindex_counts_weighted(const float* time, const float* event, const f
 int advmil_cindex_counts_weighted_plan(int* row_tile, int* resample_chunk, int* max_chunk_blocks);
 
 /* ------------------------------------------------------------------------------------------
+ * Risk-group stratification, csrc/strat.hip: the log-rank sums and the Kaplan-Meier curves of R rows over one cohort of n samples.
+ * A row is a vector of group bits (a label permutation, a cut point) and / or of integer weights (a bootstrap resample); a weighted row
+ * is by definition the unweighted computation on the arrays in which sample i stands weights[r, i] times.
+ * The cohort, prepared once by the caller: order[n] (int32) = a stable ascending sort of the times, stime[k] = time[order[k]] (ascending:
+ * the caller's duty, a device array cannot be checked here), sevent[k] = event[order[k]] (!= 0: event observed). The rows stay in the
+ * caller's sample order and are read through `order`: groups[R, ldg] (uint8, 0 / not 0; ldg == 0: one row shared by all, else ldg >= n),
+ * weights[R, ldw] (int32, every entry >= 0, ldw >= n; NULL: all ones). An entry of `order` outside [0, n) is read as 0: no address
+ * outside a row is ever formed. sum_i weights[r, i] < 2^31 per row is the caller's duty. at[Q]: ascending query times, Q >= 0.
+ * With w, e, g a row's weights, event flags and group bits, and over the distinct times t_j: d_j = sum of w e at t_j, n_j = sum of w
+ * over time >= t_j, d1_j and n1_j their group-1 parts, n0_j = n_j - n1_j (all exact integers):
+ *   counts[r, 0..5] (int64) = sum w e g (observed events of group 1), sum w e, sum w g, sum w, #{j: d_j > 0}, #{j: d_j > 0, n_j > 1};
+ *   sums[r, 0..1] (double) = E1 = sum_{j: d_j > 0} d_j n1_j / n_j and V = sum_{j: d_j > 0, n_j > 1} (n1_j / n_j) (n0_j / n_j) d_j
+ *     ((n_j - d_j) / (n_j - 1)) (the hypergeometric variance, from quotients: the product of the four counts overflows 64 bits);
+ *   km[r, c, q] (double, only if Q > 0), c = group 0, group 1, pooled: prod_{t_j <= at[q]} (n^c_j - d^c_j) / n^c_j over the blocks with
+ *     d^c_j > 0 -- an empty product is exactly 1, a factor with d == n exactly 0, a class with nobody at risk keeps its value;
+ *   median[r, c] (double): the first event time at which that product is <= 0.5, +inf if it never is.
+ * Every output slot is written. A row's outputs depend on that row's inputs only (not on R, its position or what the buffers held);
+ * no atomics, a fixed order of every sum and product: the same bits from run to run. ws: 4-byte aligned, >=
+ * advmil_logrank_rows_workspace_bytes(n, Q) (a pure host function; 0 for Q == 0, ws may then be NULL), else ADVMIL_EWORKSPACE.
+ * 1 <= n, R <= 2^20, 0 <= Q <= 2^16, 4-byte (stime, sevent, order, weights, at, ws) and 8-byte (counts, sums, km, median) alignment,
+ * else ADVMIL_EINVAL before anything is enqueued. Asynchronous on `stream`, capturable, no host synchronisation. */
+size_t advmil_logrank_rows_workspace_bytes(int64_t n, int Q);
+int advmil_logrank_rows(const float* stime, const float* sevent, const int32_t* order, int64_t n, const uint8_t* groups, int64_t ldg,
+                        const int32_t* weights, int64_t ldw, int R, const float* at, int Q, int64_t* counts, double* sums, double* km,
+                        double* median, void* ws, size_t ws_bytes, advmil_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Survival evaluators (eval/evaluator.py:11,133,213) and the two O(n^2) pair losses (loss/utils.py:43-80, 155-175), csrc/survk.hip.
  * fp32 inputs; every term is formed in fp32 (exp / log of a term: the hardware v_exp_f32 / v_log_f32, ~1 ulp), every sum is carried
  * in double; per-anchor logs and the rescaling of the softmax merge are double-precision libm. No floating-point atomics: partials go
