@@ -530,7 +530,17 @@ __device__ __forceinline__ void gemm_epilogue_stream(const GemmArgs& g, f32x16 (
               make_float4(res[q][0], res[q][1], res[q][2], res[q][3]);
         continue;
       }
-      if (out) {         // (NULL: the caller wants the operand planes of the result only -- advmil_gemm_f32_tiled with C == NULL and c_hi set)
+      if (gpair) {
+        // the training gate activations ([rows, 2D], 403 MB at the 16-bag slab): nothing reads them before gate_bwd, more than an
+        // Infinity Cache of other traffic later. Stored as always they sit dirty in the cache and the NEXT launch (the pooling pass, which
+        // is HBM-bound) pays their write-back; streaming stores move it under this contraction, which is not.
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          const int64_t off = (rbase + a * 32 + q * 8 + rq) * ldo + col;
+          const f32x4 v4 = {res[q][0], res[q][1], res[q][2], res[q][3]};
+          __builtin_nontemporal_store(v4, reinterpret_cast<f32x4*>(out + off));
+        }
+      } else if (out) {  // (NULL: the caller wants the operand planes of the result only -- advmil_gemm_f32_tiled with C == NULL and c_hi set)
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
           const int64_t off = (rbase + a * 32 + q * 8 + rq) * ldo + col;

@@ -72,7 +72,7 @@ extern "C" int advmil_gemm_f32_plan_layout(int a_kc, int b_kc, int64_t M, int64_
   return plan_exact(M, N, K, tile, splits);
 }
 
-// Tile of the plane-fed NT kernel for this shape (82 / 83), or 0 when the shape does not qualify (then the generic kernel runs).
+// Tile of the plane-fed NT kernel for this shape (82 / 83, or 87 for a deep N = 128 slab), or 0 when the shape does not qualify (then the generic kernel runs).
 extern "C" int advmil_gemm_f32_plan_planes(int a_kc, int b_kc, int64_t M, int64_t N, int64_t K, int* tile) {
   if (!tile) return ADVMIL_EINVAL;
   *tile = 0;
@@ -89,6 +89,9 @@ extern "C" int advmil_gemm_f32_plan_planes(int a_kc, int b_kc, int64_t M, int64_
   static const int min_tiles = []() { const char* e = getenv("ADVMIL_NT_PLANES_MIN_TILES"); return e ? atoi(e) : 256; }();
   // one 8-wave workgroup per CU: less than one full wave of tiles loses to the small tiles. (384 -- 1.5 waves -- until round 4; 256
   // measured +0.9 % on the PatchGCN step, whose 65536 x 128 layers are exactly one wave, and neutral at 1-5 ABMIL bags and ESAT 8k)
+  // N = 128: the whole weight matrix is one column tile, so every 256-row tile stages all of B again beside its rows of A. 512-row tiles
+  // (code 87) halve that, once they still give every CU a tile. ADVMIL_NT_PLANES_TN=2 keeps 256x128 (the same-build A/B switch).
+  if (N == 128 && M % 512 == 0 && M / 512 >= min_tiles && !(force && force[0] == '2')) { *tile = 87; return ADVMIL_OK; }
   const int64_t nt_ = (M / 256) * (N / (64 * tnp));
   if (nt_ < min_tiles && !(tnp == 2 && N % 192 == 0 && nt_ >= 192)) return ADVMIL_OK;
   *tile = 80 + tnp;
@@ -168,6 +171,7 @@ static int tile_wc(int tile) { return (tile == 34 || tile == 24) ? 4 : 2; }
 extern "C" int advmil_gemm_f32_gate_blocks(int tile, int64_t N) {
   if (tile >= 82 && tile <= 84) return (int)(N / (64 * (tile % 10))) * 2;      // plane-fed NT kernel: 2 waves along N
   if (tile == 85 || tile == 86) return (int)(N / (64 * (tile == 85 ? 4 : 2))) * 2;   // (its plain forms: the training gate score)
+  if (tile == 87) return 0;                                                          // (512x128: bias + activation only, no gate score)
   if (g_gemm_mode != 1) {
     if (tile / 10 == 4) tile = 20 + tile % 10;
     else if (tile % 10 == 4) tile = (tile / 10 == 3) ? 23 : 22;
@@ -185,6 +189,8 @@ static bool tile_geom(int tile, int& tm, int& tn, int& wr, int& wc) {
     case 24: tm = 2; tn = 2; wr = 2; wc = 4; return true;
     case 23: case 22: case 13: case 12: case 11: tm = tile / 10; tn = tile % 10; wr = 2; wc = 2; return true;
     case 83: case 82: tm = 2; tn = tile % 10; wr = 4; wc = 2; return true;      // plane-fed NT kernel, full epilogue (256x192 / 256x128)
+    // its plain forms carry none of what asks for a geometry here (mask bits, column sums): 256x256, 256x128 and 512x128 (4 x 2 blocks per wave)
+    case 85: case 86: case 87: return false;
     default: return false;
   }
 }
@@ -194,6 +200,12 @@ extern "C" int64_t advmil_gemm_f32_colsum_rows(int tile, int64_t M, int64_t N) {
   if (g_gemm_mode != 1 || !tile_geom(tile, tm, tn, wr, wc) || tm * tn < 4) return 0;
   const int64_t bm = 32 * tm * wr, bn = 32 * tn * wc;
   return ((M % bm) || (N % bn)) ? 0 : (M / bm) * wr;
+}
+
+// CUs of the current device (asked once): the grid of the persistent plane-fed NT kernel
+static int device_cus() {
+  static const int ncu = []() { int dev = 0, n = 0; hipGetDevice(&dev); hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev); return n > 0 ? n : 256; }();
+  return ncu;
 }
 
 extern "C" int advmil_merge_partials(const float* partial, int nblk, int64_t stride, int64_t ncols, float* out, int accumulate,
@@ -278,6 +290,18 @@ extern "C" int advmil_gemm_f32_tiled(int a_kc, int b_kc, int64_t M, int64_t N, i
   // NT form with both operands as planes: the LDS-DMA kernel (tile codes 82 / 83 = 256 x 128 / 192, 8 waves). The plan
   // (advmil_gemm_f32_plan_planes, or tile 0 here) picks it whenever the shape qualifies; ADVMIL_NT_PLANES=0 turns it off.
   if (tile == 0 && pre == 3 && splits == 1) { int t = 0; advmil_gemm_f32_plan_planes(a_kc, b_kc, M, N, K, &t); if (t) tile = t; }
+  if (tile == 87) {
+    // 512x128 with the PLAIN streaming epilogue, for the N = 128 layers of a deep slab (B is one column tile: staged once per 512 rows
+    // instead of once per 256). Bias + activation (+ planes) only; one layer, one column tile, no split-K.
+    if (epi->gate_wc || epi->rowv || epi->maskref || epi->maskbits || epi->colsum || epi->accumulate || epi->c2 || (epi->seed && epi->drop_p > 0.0f))
+      return ADVMIL_EINVAL;
+    if (g_gemm_mode != 1 || !a_kc || !b_kc || pre != 3 || splits != 1 || (M % 512) || N != 128 || K < 64 || (K % 32) || !epi->b_lo) return ADVMIL_EINVAL;
+    if ((uint64_t)M * (uint64_t)lda * 2 >= (1ull << 32) || (uint64_t)N * (uint64_t)ldb * 2 >= (1ull << 32)) return ADVMIL_EINVAL;   // 32-bit plane offsets
+    g.mtiles = (int)(M / 512);
+    g.ntiles = 1;
+    const int cus = device_cus();
+    return advmil_launch_nt_planes(tile, !epi->a_lo, dim3(g.mtiles < cus ? g.mtiles : cus), stream, g);      // persistent, as below
+  }
   if (tile >= 82 && tile <= 86) {
     // 86: 256x128 with the PLAIN streaming epilogue (like 85): the two-layer launch of a slab too short to fill the chip with 256x256 tiles
     const int tnp = tile == 85 ? 4 : tile == 86 ? 2 : tile % 10, bm = 256, bkt = 32;
@@ -299,7 +323,7 @@ extern "C" int advmil_gemm_f32_tiled(int a_kc, int b_kc, int64_t M, int64_t N, i
     if ((uint64_t)M * (uint64_t)lda * 2 >= (1ull << 32) || (uint64_t)N * (uint64_t)ldb * 2 >= (1ull << 32)) return ADVMIL_EINVAL;   // 32-bit plane offsets
     g.mtiles = (int)(M / bm);
     g.ntiles = (int)(N / (64 * tnp));
-    static const int ncu = []() { int dev = 0, n = 0; hipGetDevice(&dev); hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev); return n > 0 ? n : 256; }();
+    const int ncu = device_cus();
     const int ntile_all = g.mtiles * g.ntiles;
     dim3 pgrid(ntile_all < ncu ? ntile_all : ncu);        // persistent: one workgroup per CU walks its share of the tiles
     if (!epi->b_lo) return ADVMIL_EINVAL;                 // (a single-plane B has no instantiation here: weights are always hi + lo)

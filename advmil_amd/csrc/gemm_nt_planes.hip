@@ -6,7 +6,7 @@
 // rows, B = a weight matrix). With both operands pre-split there is nothing to convert, so the tile goes global -> LDS by the
 // gfx950 LDS-DMA (global_load_lds_dwordx4: 16 bytes per lane, no VGPR round trip, no VALU), the inner loop is ds_read_b128 + MFMA
 // only, and the next chunk's DMA flies under the current chunk's MFMAs.
-//   workgroup = WR x 2 waves, each wave a 64 x (32*TN) accumulator block -> tile (64*WR) x (64*TN):
+//   workgroup = WR x 2 waves, each wave a (32*TM) x (32*TN) accumulator block (TM = 2 but for the 512x128 form) -> tile (32*TM*WR) x (64*TN):
 //     WR = 4 (8 waves, one workgroup per CU): 256x128 / 256x192, k chunks of 32 -- the instantiated forms (256x256 measured equal);
 //     WR = 2 (4 waves, two workgroups per CU, whose prologue / epilogue would hide under the other's K loop): 128x128 (k 32)
 //       measured equal, 128x192 / 128x256 (k 16, 32-byte DMA rows) 10-15 % slower than the 8-wave forms on every slab shape, so
@@ -16,7 +16,7 @@
 //     the DMA writes lane-linear (piece base + 16 * lane), so the swizzle is applied to each lane's SOURCE address: the lane that
 //     fills stored position q of row r fetches unit ps_unit(r, q) of that row (same involution as the fragment reads);
 //   one piece = 1 KB = one wave-instruction = 16 rows x 64 B (k 32) or 32 rows x 32 B (k 16).
-// Requirements (checked by the host): M % (64*WR) == 0, N % (64*TN) == 0, K % BKT == 0, planes 16-byte aligned with ld % 8 == 0,
+// Requirements (checked by the host): M % (32*TM*WR) == 0, N % (64*TN) == 0, K % BKT == 0, planes 16-byte aligned with ld % 8 == 0,
 // splits == 1.
 // =====================================================================================
 
@@ -30,10 +30,14 @@
 // 256x256 form, which beside the full streaming epilogue would not fit the register file. EPI = 2: 256x256 with the PLAIN streaming form.
 // ALO = 0: A is a single-plane (bf16) operand -- no A lo rows in the ring (a 256x256 chunk stages 48 KB instead of 64), two MFMAs
 // per product (a.b = ah.bh + ah.bl exactly as the three-product form with al = 0: same order, bit-identical to it).
-template <int TN, int NBUF, int WR, int BKT, int EPI = 0, int ALO = 1>
+// TM = 4 (with TN = 2, WR = 4: tile code 87): 512x128, a 128 x 64 block per wave -- the same MFMAs and fragment reads per chunk as the
+// 256x256 form. For the N = 128 slab layers, where the whole weight matrix is ONE column tile and every row tile stages all of B again
+// next to its own rows of A: 512 rows per tile halve that share of the per-CU staging path (D's patch embedding 157 -> 146 us in the step). Two slots of 80 KB are
+// exactly the CU's 160 KB of LDS; the plain streaming epilogue only (the full one does not fit beside 8 accumulator blocks per wave).
+template <int TN, int NBUF, int WR, int BKT, int EPI = 0, int ALO = 1, int TM = 2>
 __global__ __launch_bounds__(128 * WR, 2) void gemm_nt_planes_kernel(GemmArgs g) {
-  constexpr int TM = 2, WC = 2, NW = WR * WC;
-  constexpr int BM_ = 64 * WR, BN_ = 64 * TN;
+  constexpr int WC = 2, NW = WR * WC;
+  constexpr int BM_ = 32 * TM * WR, BN_ = 64 * TN;
   constexpr int AROWS = (1 + ALO) * BM_;               // plane rows of A per buffer
   constexpr int ROWS_ALL = AROWS + 2 * BN_;            // plane rows per buffer: A hi, (A lo,) B hi, B lo
   constexpr int RPP = 512 / BKT, LPR = BKT / 8;        // rows per 1 KB piece, lanes (16-byte units) per row
@@ -191,6 +195,7 @@ int advmil_launch_nt_planes(int tile, bool a_single, dim3 pgrid, hipStream_t str
       case 86: hipLaunchKernelGGL((gemm_nt_planes_kernel<2, 3, 4, 32, 2, 0>), pgrid, dim3(512), 0, stream, g); break;
       case 83: hipLaunchKernelGGL((gemm_nt_planes_kernel<3, 2, 4, 32, 0, 0>), pgrid, dim3(512), 0, stream, g); break;
       case 82: hipLaunchKernelGGL((gemm_nt_planes_kernel<2, 3, 4, 32, 0, 0>), pgrid, dim3(512), 0, stream, g); break;
+      case 87: hipLaunchKernelGGL((gemm_nt_planes_kernel<2, 2, 4, 32, 2, 0, 4>), pgrid, dim3(512), 0, stream, g); break;   // 2 x 48 KB + the patch
       default: return ADVMIL_EINVAL;
     }
     ADVMIL_LAUNCH_CHECK();
@@ -202,6 +207,7 @@ int advmil_launch_nt_planes(int tile, bool a_single, dim3 pgrid, hipStream_t str
     case 86: hipLaunchKernelGGL((gemm_nt_planes_kernel<2, 3, 4, 32, 2>), pgrid, dim3(512), 0, stream, g); break;   // 256x128, plain streaming epilogue (+ two layers)
     case 83: hipLaunchKernelGGL((gemm_nt_planes_kernel<3, 2, 4, 32>), pgrid, dim3(512), 0, stream, g); break;   // 2 x 56 KB
     case 82: hipLaunchKernelGGL((gemm_nt_planes_kernel<2, 3, 4, 32>), pgrid, dim3(512), 0, stream, g); break;   // 3 x 48 KB: two chunks in flight
+    case 87: hipLaunchKernelGGL((gemm_nt_planes_kernel<2, 2, 4, 32, 2, 1, 4>), pgrid, dim3(512), 0, stream, g); break;   // 512x128, plain streaming epilogue: 2 x 80 KB
     default: return ADVMIL_EINVAL;
   }
   ADVMIL_LAUNCH_CHECK();

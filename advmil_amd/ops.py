@@ -297,7 +297,7 @@ def gemm_plan(M, N, K, a_kc=True, b_kc=True):
 
 
 def gemm_plan_planes(M, N, K, a_kc=True, b_kc=True):
-    """Tile code (82 / 83) of the plane-fed LDS-DMA kernel for an NT contraction whose operands both come as Planes, or 0."""
+    """Tile code (82 / 83, 87 for a deep N = 128 slab) of the plane-fed LDS-DMA kernel for an NT contraction whose operands both come as Planes, or 0."""
     key = ("pl", M, N, K, bool(a_kc), bool(b_kc), _mode_code())
     if key not in _PLAN_CACHE:
         t = ctypes.c_int(0)
@@ -525,7 +525,7 @@ def gemm(A, B, a_kc, b_kc, M, N, K, out=None, ldc=None, bias=None, act0=0, act1=
     b_single = False
     planes_only_b = B is None                 # B exists as (two) planes only (Wab^T of the pooling backward's dh): plane-fed kernels only
     if planes_only_b:
-        if b_planes is None or b_planes.single or get_gemm_mode() != "bf16x3" or not (82 <= tile <= 86 or 91 <= tile <= 93):
+        if b_planes is None or b_planes.single or get_gemm_mode() != "bf16x3" or not (82 <= tile <= 87 or 91 <= tile <= 93):
             raise ValueError("gemm(B=None) needs two-plane b_planes, bf16x3 mode and a plane-fed tile")
         B = b_planes.hi                       # (pointer and pitch only: never read as fp32)
     elif is_bf16_slab(B):
@@ -542,6 +542,9 @@ def gemm(A, B, a_kc, b_kc, M, N, K, out=None, ldc=None, bias=None, act0=0, act1=
         ptile = gemm_plan_planes(M, N, K, a_kc, b_kc)          # both operands pre-split: the plane-fed LDS-DMA kernel, if the shape fits
         if ptile:
             tile, splits = ptile, 1
+            if ptile == 87 and (gate_wc is not None or rowv is not None or maskref is not None or maskbits is not None or colsum is not None
+                                or accumulate or (drop_p > 0.0 and seed is not None)):
+                tile = 82                                      # 512x128 is a plain form (bias + activation, + planes): everything else stays on 256x128
             if gate_wc is not None and gate_bits is not None:
                 tile = 85 if (N % 256 == 0 and (M // 256) * (N // 256) >= 256) else 86      # training form: a plain tile, C written too
             elif gate_wc is not None and N % 256 == 0 and (M // 256) * (N // 256) >= 384:
@@ -633,18 +636,18 @@ def gemm(A, B, a_kc, b_kc, M, N, K, out=None, ldc=None, bias=None, act0=0, act1=
         # right for the optimizer's gradient arena, which nothing reads before the step, wrong for any other destination -- the next
         # launch would read C without the partials. Such a call takes the fold-free plan.
         splits = 1
-    if (b_only and not (91 <= tile <= 93) and not (82 <= tile <= 86 and not b_single) and tile not in (22, 12, 11)
+    if (b_only and not (91 <= tile <= 93) and not (82 <= tile <= 87 and not b_single) and tile not in (22, 12, 11)
             and not (tile in (34, 24) and not a_kc and not b_kc)):
-        # a bf16 / planes-only B operand has no fp32 image: land on a kernel that stages B from its plane(s). (82-86 read two-plane
+        # a bf16 / planes-only B operand has no fp32 image: land on a kernel that stages B from its plane(s). (82-87 read two-plane
         # operands from their planes and nothing else: a B whose fp32 image is stale stays there, as B=None does)
         tile = 22
-    if planes_only_a and a_planes.single and not (82 <= tile <= 86) and tile not in (22, 12, 11):
+    if planes_only_a and a_planes.single and not (82 <= tile <= 87) and tile not in (22, 12, 11):
         tile = 22                             # (single-plane A: only these forms are built for it)
-    if planes_only_a and a_planes.fp32_stale and not (82 <= tile <= 86) and not (91 <= tile <= 93) and tile not in (22, 12, 11) \
+    if planes_only_a and a_planes.fp32_stale and not (82 <= tile <= 87) and not (91 <= tile <= 93) and tile not in (22, 12, 11) \
             and not pre_a_tile_ok(tile, a_kc, b_kc, b_planes is not None):
         tile = 22                             # (a slab staged as planes only: land on a form that stages A from its planes)
-    if planes_only_a and not (82 <= tile <= 86) and not (91 <= tile <= 93) and not pre_a_tile_ok(tile if tile else gemm_plan(M, N, K, a_kc, b_kc)[0], a_kc, b_kc,
-                                                                     b_planes is not None):       # (82-85: plane-fed, reads planes only)
+    if planes_only_a and not (82 <= tile <= 87) and not (91 <= tile <= 93) and not pre_a_tile_ok(tile if tile else gemm_plan(M, N, K, a_kc, b_kc)[0], a_kc, b_kc,
+                                                                     b_planes is not None):       # (82-87: plane-fed, reads planes only)
         raise ValueError(f"gemm(A=None): tile {tile} has no pre-split-A instantiation for this layout")
     L = _lib.lib()
     wsb = L.advmil_gemm_f32_workspace_bytes(M, N, splits)
@@ -653,6 +656,7 @@ def gemm(A, B, a_kc, b_kc, M, N, K, out=None, ldc=None, bias=None, act0=0, act1=
     name = None
     if prof is not None or STAMPS is not None:
         name = ("gemm_nt_planes_kernel<%d>" % (tile - 80)) if 82 <= tile <= 84 else "gemm_nt_planes_kernel<4,plain>" if tile == 85 else "gemm_nt_planes_kernel<2,plain>" if tile == 86 else \
+            "gemm_nt_planes_kernel<2,plain,512>" if tile == 87 else \
             ("gemm_tn_planes_kernel<%d>" % tile) if 91 <= tile <= 93 else \
             "gemm_f32_kernel<%d,%d,%d,%d>" % (bool(a_kc), bool(b_kc), tile // 10, tile % 10)
     if prof is not None:
@@ -1560,6 +1564,8 @@ class GatedAttnPoolFn(torch.autograd.Function):
         # (round 6: with the first layer's activation backward in its epilogue -- ctx.act_fuse -- the launch no longer stays on the generic
         # kernel: the plane-fed kernel's full epilogue carries the rank-1 + bit-mask + column-sum form too)
         dh_tile = gemm_plan_planes(N, D, 2 * D) if (need_h and USE_PLANES and get_gemm_mode() == "bf16x3") else 0
+        if dh_tile == 87:
+            dh_tile = 82                         # (rank-1 + bit mask + column sums: the full epilogue, which the plain 512x128 form has not)
         dh_nt = bool(dh_tile and DH_NT_FUSED and ctx.act_fuse is not None and ctx.act_fuse[2] is not None
                      and getattr(ctx, "wabpl", None) is not None and int(_lib.lib().advmil_gemm_f32_colsum_rows(dh_tile, N, D)) > 0)
         # bf16x3, slab-sized: dG is consumed by exactly two contractions (dh = dG Wab, dWab = dG^T h) that would split it into hi + lo
