@@ -434,7 +434,7 @@ __global__ __launch_bounds__(256) void dx_chain_bwd_kernel(RcBwdArgs g) {
     rc_to_patch(acc[0][0], pa, lane);
     RC_WAVE_SYNC();
     const int col = nB[0] + c4;
-    const float inv1 = g.p1 > 0.f ? hw_rcp(1.f - g.p1) : 1.f;
+    const float inv1 = (g.seed && g.p1 > 0.f) ? hw_rcp(1.f - g.p1) : 1.f;      // the forward's rule: no seed, no draw, no scale
     float cs[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int q = 0; q < 4; ++q) {

@@ -703,7 +703,9 @@ int advmil_gheadk_bwd(const advmil_gheadk_t* a, advmil_stream_t stream);
  *   dG [R, 256], dfc [R, 128], dpre [R, 64] (= d h1 masked by the ReLU / dropout of h1), de [R, 128] (NULL: not wanted) are written;
  *   dwc[128], dbab[256], dbc[1], db2[128], db1[64] are ADDED into (arena slots; the merge of the per-workgroup partial rows is deferrable:
  *   advmil_defer_sums). The three weight gradients dWab = dG^T fc, dW2 = dfc^T h1, dW1 = dpre^T e stay contractions of the engine.
- *   WabT / W2T / W1T: operand planes of the TRANSPOSED weights ([128, 256], [64, 128], [128, 64]), made by advmil_dx_chain_prep. */
+ *   WabT / W2T / W1T: operand planes of the TRANSPOSED weights ([128, 256], [64, 128], [128, 64]), made by advmil_dx_chain_prep.
+ * One rule for both ways: a dropout is applied iff seed != NULL and its rate > 0. With seed == NULL neither the draws nor the
+ * 1 / (1 - p) scales of p1 and pg happen, forward and backward alike, whatever the rates say. */
 int advmil_dx_chain_fwd(const float* e, int64_t R, int d, const void* W1_hi, const void* W1_lo, const float* b1, const void* W2_hi,
                         const void* W2_lo, const float* b2, const void* Wab_hi, const void* Wab_lo, const float* bab, const float* wc,
                         const float* bc, float p1, float pg, const uint64_t* seed, uint64_t sid1, uint64_t sida, uint64_t sidb,

@@ -132,3 +132,58 @@ def test_optimizer_graph_and_evaluator_groups(L):
     assert lib.advmil_genconv_fwd(p(0), p(1), p(2), p(3), 1e-7, 100, 128, p(4), p(5), None, None) == EINVAL                  # lse without agg
     assert lib.advmil_ln_relu_mean16_bwd(p(0), p(1), p(2), p(3), p(4), p(5), 64, 128, None, p(6), p(7), 0, None, None, None, 1, p(8), 1 << 20, None) == EINVAL   # neither dy nor its planes
     assert lib.advmil_ln_relu_mean16_bwd(p(0), p(1), p(2), p(3), p(4), p(5), 64, 128, None, p(6), p(7), 0, None, p(9), None, 1, p(8), 1 << 20, None) == EINVAL   # one plane only
+
+
+# the fused region network (csrc/region.hip): argument names in the header's order, every pointer a fake aligned address
+DX_FWD = ("e", "R", "d", "W1_hi", "W1_lo", "b1", "W2_hi", "W2_lo", "b2", "Wab_hi", "Wab_lo", "bab", "wc", "bc", "p1", "pg", "seed", "sid1", "sida",
+          "sidb", "rng_row", "h1", "fc", "ab", "s", "stream")
+DX_PREP = ("W1", "W2", "Wab", "d", "W1T_hi", "W1T_lo", "W2T_hi", "W2T_lo", "WabT_hi", "WabT_lo", "stream")
+DX_BWD = ("R", "d", "ds", "A", "dpooled", "dmean", "rowseg", "seg_ptr", "dfc_add", "h1", "ab", "wc", "p1", "pg", "seed", "sida", "sidb", "rng_row",
+          "WabT_hi", "WabT_lo", "W2T_hi", "W2T_lo", "W1T_hi", "W1T_lo", "dG", "dfc", "dpre", "de", "dwc", "dbab", "dbc", "db2", "db1", "ws", "ws_bytes",
+          "stream")
+DX_SCALARS = {"R": 100, "d": 128, "p1": 0.25, "pg": 0.25, "sid1": 1, "sida": 2, "sidb": 3, "stream": None}
+
+
+def _dx_call(fn, names, **over):
+    """fn with every pointer argument a distinct fake 16-byte aligned address, the scalars valid, and `over` on top."""
+    args = {n: DX_SCALARS[n] if n in DX_SCALARS else A16 + (i << 20) for i, n in enumerate(names)}
+    args.update(over)
+    return fn(*[ctypes.c_void_p(v) if isinstance(v, int) and n not in DX_SCALARS and n != "ws_bytes" else v for n, v in ((n, args[n]) for n in names)])
+
+
+def test_fused_region_network_refuses_before_any_launch(L):
+    """advmil_dx_chain_fwd / _prep / _bwd: every refusal is ADVMIL_EINVAL (or ADVMIL_EWORKSPACE), i.e. returned by the argument checks.
+    A call that got as far as a launch would answer with a positive hipError_t on this GPU-less path."""
+    lib = L.lib()
+    need = lib.advmil_dx_chain_bwd_workspace_bytes(100, 128)
+    assert need == 2 * 580 * 4
+    fwd = lambda **o: _dx_call(lib.advmil_dx_chain_fwd, DX_FWD, **o)                              # noqa: E731
+    prep = lambda **o: _dx_call(lib.advmil_dx_chain_prep, DX_PREP, **o)                           # noqa: E731
+    bwd = lambda **o: _dx_call(lib.advmil_dx_chain_bwd, DX_BWD, **dict(dict(ws_bytes=need), **o))   # noqa: E731
+    nan = float("nan")
+    for call in (fwd, prep, bwd):
+        assert call(d=64) == EINVAL and call(d=256) == EINVAL and call(d=0) == EINVAL             # d != 128
+    for call in (fwd, bwd):
+        assert call(R=0) == EINVAL and call(R=-64) == EINVAL                                      # R <= 0
+        for k in ("p1", "pg"):                                                                    # rates outside [0, 1), NaN included
+            for v in (1.0, 1.5, -0.25, nan):
+                assert call(**{k: v}) == EINVAL, (k, v)
+    required = {fwd: ("e", "W1_hi", "W1_lo", "b1", "W2_hi", "W2_lo", "b2", "Wab_hi", "Wab_lo", "bab", "wc", "fc", "s"),
+                prep: ("W1", "W2", "Wab", "W1T_hi", "W1T_lo", "W2T_hi", "W2T_lo", "WabT_hi", "WabT_lo"),
+                bwd: ("ds", "A", "dpooled", "h1", "ab", "wc", "WabT_hi", "WabT_lo", "W2T_hi", "W2T_lo", "dG", "dfc", "dpre", "dwc", "dbab", "dbc", "db2",
+                      "db1", "ws")}
+    for call, names in required.items():
+        for k in names:
+            assert call(**{k: None}) == EINVAL, k
+    # rows are read and written 16 bytes at a time: a pointer 4 bytes off is refused
+    aligned = {fwd: ("e", "W1_hi", "W1_lo", "b1", "W2_hi", "W2_lo", "b2", "Wab_hi", "Wab_lo", "bab", "wc", "h1", "fc", "ab"),
+               bwd: ("dpooled", "dmean", "dfc_add", "h1", "ab", "wc", "WabT_hi", "WabT_lo", "W2T_hi", "W2T_lo", "W1T_hi", "W1T_lo", "dG", "dfc", "dpre",
+                     "de", "ws")}
+    for call, names in aligned.items():
+        for k in names:
+            assert call(**{k: A16 + 4}) == EINVAL, k
+    # de wanted without the planes of W1^T
+    assert bwd(W1T_hi=None) == EINVAL and bwd(W1T_lo=None) == EINVAL and bwd(W1T_hi=None, W1T_lo=None) == EINVAL
+    # a workspace one float short of a partial row per tile
+    assert bwd(ws_bytes=need - 4) == EWORKSPACE and bwd(ws_bytes=0) == EWORKSPACE
+    assert bwd(R=129, ws_bytes=need) == EWORKSPACE                                               # three tiles in a two-tile workspace

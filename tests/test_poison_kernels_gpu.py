@@ -804,6 +804,21 @@ def test_region_chain(lens, want_mean, e_grad):
         TR._close(a["grads"][k], b["grads"][k], 5e-5, k)
 
 
+def test_region_chain_direct_walk():
+    """The entry points of csrc/region.hip themselves (tests/test_region_walks_gpu.py), forward and backward, at bags [30, 1, 20, 77, 64]
+    with both draws on and a row map: three tiles whose first holds three segment ends, tail rows the kernels skip, a partial row per tile
+    with three columns nobody writes. Four runs for the bit comparison, then the walk file's own float64 body under 0xFF."""
+    from tests import test_region_walks_gpu as TRW
+    c = TRW.POISON_CASE
+    assert c.lens == (30, 1, 20, 77, 64) and c.mode == "both"
+
+    def fn():
+        fw = TRW.launch_fwd(sum(c.lens), c.mode, c.rmap)
+        return dict(fw=fw, bw=TRW.launch_bwd(c, fw, nan_ws=False))
+    runs(fn)
+    under_ff(TRW.body_bwd, c, False)
+
+
 @pytest.mark.parametrize("M,N,K", [(5, 30, 36), (17, 260, 1028)])
 def test_small_linear(ops, M, N, K):
     g = torch.Generator().manual_seed(M * 1000 + N + K)
