@@ -3,5 +3,7 @@ from .bootstrap import (bootstrap_concordance_index, bootstrap_concordance_sampl
                         multiplicities, paired_bootstrap_concordance, resample_indices)
 from .stratify import (kaplan_meier, logrank_from_rows, logrank_permutation_test, logrank_rows, logrank_scan, logrank_test,  # noqa: F401
                        permutation_groups, risk_groups, stratify)
+from .timedep import (bootstrap_timedep, brier_score, cumulative_dynamic_auc, default_times, integrated_brier_score, ipcw_rows,  # noqa: F401
+                      statistics_from_rows, survival_from_hazards, survival_from_samples)
 from .evaluator import ContSurv_Evaluator, DiscSurv_Evaluator, CoxSurv_Evaluator  # noqa: F401
 from .utils import prepare_evaluator  # noqa: F401

@@ -20,6 +20,7 @@ from ..loss import utils as LU
 from .bootstrap import bootstrap_concordance_index, bootstrap_risk
 from .cindex import concordance_index, concordance_index_censored
 from .stratify import _risks, stratify_risk
+from . import timedep as TD
 
 _WHICH = {"bce": 0, "hinge": 1, "wasserstein": 2}
 # slots of the result array (doubles): [0, 16) the family's fused sums, [16, 20) rank_loss state, [20, 22) SurvPLE
@@ -127,6 +128,29 @@ class _Evaluator(object):
                 "median_high": s.median_high, "z": s.z, "chi2": s.chi2, "p": s.p, "p_perm": s.p_perm, "z_lo": s.z_lo, "z_hi": s.z_hi,
                 "n_undefined": s.n_undefined}
 
+    def _survival_estimate(self, data, times):
+        """-> (event, time, at, surv [n, Q] or None, risk [n] or [n, Q]) on the device: what `time_dependent` scores."""
+        e, t, risk = self._risk_estimate(data)
+        return e, t, (TD.default_times(e, t) if times is None else times), None, risk
+
+    def time_dependent(self, data, times=None, n_boot=0, seed=0, level=0.95):
+        """Calibration and discrimination of the predicted survival function over time (eval/timedep.py, one launch): the IPCW Brier
+        score `brier` and the cumulative/dynamic AUC `auc` at `times` (default: the deciles of the observed event times below the
+        largest time; bin indices for a discrete-time model), their summaries `ibs` and `mean_auc`, NaN where undefined; with
+        `n_boot` > 0 the percentile intervals `<key>_lo` / `<key>_hi` at `level` and `n_undefined`, per statistic the resamples in
+        which it is undefined (more than 5 % of them: ValueError). An evaluator without a survival function has no `brier` / `ibs`."""
+        e, t, at, surv, risk = self._survival_estimate(data, times)
+        b = TD.bootstrap_timedep(e, t, at, surv, risk, n_boot=n_boot, seed=seed, level=level)
+        out = {"times": b.at}
+        for k in ("brier", "ibs", "auc", "mean_auc"):
+            if hasattr(b, k):
+                out[k] = getattr(b, k)
+                if n_boot > 0:
+                    out[k + "_lo"], out[k + "_hi"] = getattr(b, k + "_lo"), getattr(b, k + "_hi")
+        if n_boot > 0:
+            out["n_undefined"] = b.n_undefined
+        return out
+
 
 class ContSurv_Evaluator(_Evaluator):
     """Performance evaluator for continuous survival model"""
@@ -196,6 +220,20 @@ class ContSurv_Evaluator(_Evaluator):
             elif m == "nonevent_t_nre":
                 out[m] = _mean(r[8], n_non)
         return out
+
+    def _survival_estimate(self, data, times):
+        """The survival function is the empirical one of the generator's sampled times `dist_y_hat` [n, S, 1]; the risk at t is 1 - S(t)."""
+        if data.get("dist_y_hat") is None:
+            raise ValueError("time_dependent scores the predicted distribution: the collector holds no 'dist_y_hat' "
+                             "(run test_model with times_test_sample > 1)")
+        dev = _device_of(data)
+        y = _f32(data["y"], dev)
+        t, e = y[:, 0].contiguous(), y[:, 1].contiguous()
+        dist = _f32(data["dist_y_hat"], dev)
+        dist = dist.reshape(dist.shape[0], -1)
+        at = TD.default_times(e, t) if times is None else times
+        surv = TD.survival_from_samples(dist, at)
+        return e, t, at, surv, 1.0 - surv
 
 
 class DiscSurv_Evaluator(_Evaluator):
@@ -296,6 +334,22 @@ class DiscSurv_Evaluator(_Evaluator):
         _lib.check(L.advmil_surv_metrics_disc(_p(hz), hz.stride(0), _p(t), _p(e), None, n, bins, 0.0, 1e-7, 0, _p(risk), _p(res), _p(ws), wsb,
                                               _stream(dev)), "surv_metrics_disc")
         return e, t, -risk
+
+    def _survival_estimate(self, data, times):
+        """The survival function is the product of the hazards' complements; times are bin indices (default: 0 ... bins - 2 below the
+        largest observed bin, beyond which nothing is defined); the risk at t is 1 - S(t)."""
+        dev = _device_of(data)
+        y = _f32(data["y"], dev)
+        t, e = y[:, 0].contiguous(), y[:, 1].contiguous()
+        hz = _f32(data["avg_y_hat"] if "avg_y_hat" in data else data["y_hat"], dev)
+        hz = hz.reshape(hz.shape[0], -1)
+        if times is None:
+            times = torch.arange(max(hz.shape[1] - 1, 1), device=dev, dtype=torch.float32)
+            times = times[times < t.max()]
+            if times.numel() == 0:
+                raise ValueError("time_dependent: no bin index lies below the largest observed bin")
+        surv = TD.survival_from_hazards(hz, times)
+        return e, t, times, surv, 1.0 - surv
 
 
 class CoxSurv_Evaluator(_Evaluator):

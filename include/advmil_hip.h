@@ -791,6 +791,47 @@ int advmil_logrank_rows(const float* stime, const float* sevent, const int32_t* 
                         double* median, void* ws, size_t ws_bytes, advmil_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Time-dependent evaluation, csrc/timedep.hip: what the IPCW Brier score (Graf et al.) and the cumulative/dynamic AUC(t) (Uno et al.,
+ * Hung & Chiang) are made of, for R rows of integer weights (bootstrap resamples) over one cohort of n samples at Q query times. A
+ * weighted row is by definition the unweighted computation on the arrays in which sample i stands weights[r, i] times.
+ * The cohort is prepared as for advmil_logrank_rows: order[n] (int32) = a stable ascending sort of the times, stime[k] = time[order[k]],
+ * sevent[k] = event[order[k]] (!= 0: observed). Everything else stays in the caller's sample order and is read through `order` (an entry
+ * outside [0, n) is read as 0): weights[R, ldw] (int32, >= 0, ldw >= n; NULL: all ones; every row sum < 2^31: the caller's duty),
+ * surv[n, lds] (fp32, lds >= Q): surv[i, q] = the predicted probability that sample i survives at[q]; NULL: A = B = 0.
+ * risk[n, ldr] (fp32, risk_cols = 1: one column for every q, or risk_cols = Q: column q for at[q]; ldr >= risk_cols); NULL: C = 0.
+ * at[Q]: ascending (the caller's duty). No NaN anywhere (the caller's duty).
+ * Over the distinct times u of a row's samples with w > 0: n(u) = sum w [y >= u], d(u) = sum w [e][y = u], c(u) = sum w [!e][y = u];
+ *   G(t)    = prod_{u <= t, c(u) > 0} (n(u) - d(u) - c(u)) / (n(u) - d(u))   the censoring Kaplan-Meier estimate, right-continuous,
+ *             events before censorings at a tied time;
+ *   S_KM(t) = prod_{u <= t, d(u) > 0} (n(u) - d(u)) / n(u); an empty product is exactly 1.
+ * With t = at[q], cases = {i: e_i, y_i <= t}, controls = {j: y_j > t}:
+ *   counts[r, q, 0..1] (int64) = N_case = sum_cases w_i, N_ctrl = sum_controls w_j;
+ *   rowcnt[r, 0..1]    (int64) = sum w, sum w e;
+ *   sums[r, q, 0..5]  (double) = A  = sum_cases w_i surv[i, q]^2 / G(y_i),
+ *                                B  = sum_controls w_j (1 - surv[j, q])^2,
+ *                                G(at[q]), S_KM(at[q]),
+ *                                Wc = sum_cases w_i / G(y_i),
+ *                                C  = sum_cases (w_i / G(y_i)) K_i / 2, K_i = sum_controls w_j (2 [risk_i > risk_j] + [risk_i == risk_j])
+ *                                     (fp32 comparisons; K_i is an exact integer below 2^32).
+ *   Brier score(t) = (A + B / G(t)) / sum w, defined iff N_ctrl > 0; AUC(t) = C / (Wc N_ctrl), defined iff N_ctrl > 0 and N_case > 0.
+ *   Where N_ctrl > 0 every G that is divided by is > 0 (a sample beyond t is still at risk). Where N_ctrl == 0, A, Wc and C are
+ *   written as 0 (G(y_i) may be 0 there).
+ * Every output slot is written. A row's outputs depend on that row's inputs only (not on R, its position or what the buffers held); no
+ * atomics, a fixed order of every sum and product: the same bits from run to run. Each of A, B, G, S_KM, Wc, C is a sum of at most n
+ * non-negative terms or a product of at most n factors of correctly rounded quotients of exact integers: relative error <= 2 n 2^-52.
+ * ws: 8-byte aligned, >= advmil_ipcw_rows_workspace_bytes(n, R, Q) (a pure host function: R n doubles for G at every sorted sample's
+ * own time, n + Q int32 rounded up to 8 bytes; 0 for a shape outside the limits), else ADVMIL_EWORKSPACE. 1 <= n <= 2^16, 1 <= R <= 2^20,
+ * 1 <= Q <= 4096, 4-byte (stime, sevent, order, weights, at, surv, risk) and 8-byte (counts, rowcnt, sums, ws) alignment, else
+ * ADVMIL_EINVAL before anything is enqueued. Asynchronous on `stream`, capturable, no host synchronisation.
+ * advmil_ipcw_rows_plan: the walks' constants (pure host function): rows per workgroup and sorted samples per trip of the per-row walk,
+ * threads = cases per round = controls per LDS tile of the pair pass, rows a pair-pass workgroup carries. */
+size_t advmil_ipcw_rows_workspace_bytes(int64_t n, int R, int Q);
+int advmil_ipcw_rows(const float* stime, const float* sevent, const int32_t* order, int64_t n, const int32_t* weights, int64_t ldw, int R,
+                     const float* at, int Q, const float* surv, int64_t lds, const float* risk, int64_t ldr, int risk_cols,
+                     int64_t* counts, int64_t* rowcnt, double* sums, void* ws, size_t ws_bytes, advmil_stream_t stream);
+int advmil_ipcw_rows_plan(int* walk_rows, int* walk_trip, int* pair_tile, int* pair_rows);
+
+/* ------------------------------------------------------------------------------------------
  * Survival evaluators (eval/evaluator.py:11,133,213) and the two O(n^2) pair losses (loss/utils.py:43-80, 155-175), csrc/survk.hip.
  * fp32 inputs; every term is formed in fp32 (exp / log of a term: the hardware v_exp_f32 / v_log_f32, ~1 ulp), every sum is carried
  * in double; per-anchor logs and the rescaling of the softmax merge are double-precision libm. No floating-point atomics: partials go
