@@ -13,6 +13,7 @@ reference does. There is no CPU fallback."""
 import ctypes
 import functools
 
+import numpy as np
 import torch
 
 from .. import _lib
@@ -21,6 +22,7 @@ from .bootstrap import bootstrap_concordance_index, bootstrap_risk
 from .cindex import concordance_index, concordance_index_censored
 from .stratify import _risks, stratify_risk
 from . import timedep as TD
+from . import concordance as CC
 
 _WHICH = {"bce": 0, "hinge": 1, "wasserstein": 2}
 # slots of the result array (doubles): [0, 16) the family's fused sums, [16, 20) rank_loss state, [20, 22) SurvPLE
@@ -150,6 +152,44 @@ class _Evaluator(object):
         if n_boot > 0:
             out["n_undefined"] = b.n_undefined
         return out
+
+    def concordance(self, data, tau=None, n_boot=0, seed=0, level=0.95):
+        """Global discrimination beyond `c_index` (eval/concordance.py, one call): Uno's C `c_uno` at the truncation times `tau` (None:
+        no truncation) and the unweighted `c_harrell` of the risk the `c_index` metric ranks by; for an evaluator with a survival
+        function also Antolini's time-dependent concordance `c_td`, its tie-adjusted form `c_td_adj` and `c_uno_td` (Antolini's pairs,
+        Uno's weights), the survival function taken at every observed event time. NaN where undefined; with `n_boot` > 0 the percentile
+        intervals `<key>_lo` / `<key>_hi` at `level` and `n_undefined` (more than 5 % of the resamples: ValueError)."""
+        e, t, risk = self._risk_estimate(data)
+        at, col, surv = self._survival_at_event_times(data, e, t)
+        b = CC.bootstrap_concordance(e, t, risk=risk, surv=surv, col=col, tau=tau, n_boot=n_boot, seed=seed, level=level)
+        out = {"tau": b.tau}
+        for k in ("c_uno", "c_harrell", "c_td", "c_td_adj", "c_uno_td"):
+            if hasattr(b, k):
+                out[k] = getattr(b, k)
+                if n_boot > 0:
+                    out[k + "_lo"], out[k + "_hi"] = getattr(b, k + "_lo"), getattr(b, k + "_hi")
+        if n_boot > 0:
+            out["n_undefined"] = b.n_undefined
+        return out
+
+    def _survival_at_event_times(self, data, e, t, chunk=256):
+        """-> (at, col, surv [n, Q] on the device) from `_survival_estimate` at the distinct event times, `chunk` columns at a time (the
+        sampled distribution is compared with `chunk` times at once, never with all of them); (None, None, None) for an evaluator
+        without a survival function."""
+        ev = e.cpu().numpy() != 0
+        if not ev.any():
+            raise ValueError("concordance: the cohort has no observed event")
+        at = np.unique(t.to(torch.float32).cpu().numpy()[ev])
+        parts = []
+        for c0 in range(0, at.size, chunk):
+            s = self._survival_estimate(data, torch.from_numpy(at[c0:c0 + chunk]).to(t.device))[3]
+            if s is None:
+                return None, None, None
+            if not parts and at.size > CC.MAX_COLUMNS:
+                raise ValueError(f"concordance: {at.size} distinct event times, the kernel takes {CC.MAX_COLUMNS} columns; round the "
+                                 "times or evaluate a subsample")
+            parts.append(s)
+        return at, torch.from_numpy(CC.columns_at_own_times(t, at)), torch.cat(parts, dim=1)
 
 
 class ContSurv_Evaluator(_Evaluator):

@@ -832,6 +832,52 @@ int advmil_ipcw_rows(const float* stime, const float* sevent, const int32_t* ord
 int advmil_ipcw_rows_plan(int* walk_rows, int* walk_trip, int* pair_tile, int* pair_rows);
 
 /* ------------------------------------------------------------------------------------------
+ * Global concordance, csrc/concord.hip: the pair counts of Harrell's C and of Antolini's time-dependent concordance, and the sums of
+ * Uno's C, for R rows of integer weights (bootstrap resamples) over one cohort of n samples. What scikit-survival's
+ * concordance_index_ipcw and pycox's EvalSurv.concordance_td answer, restated here so that neither package is needed. A weighted row is
+ * by definition the unweighted computation on the arrays in which sample i stands weights[r, i] times.
+ * The cohort is prepared as for advmil_ipcw_rows: order[n] (int32) = a stable ascending sort of the times, stime[k] = time[order[k]],
+ * sevent[k] = event[order[k]] (!= 0: observed). Everything else stays in the caller's sample order and is read through `order` (an entry
+ * outside [0, n) is read as 0): weights[R, ldw] (int32, >= 0, ldw >= n; NULL: all ones; every row sum < 2^31: the caller's duty).
+ * Two comparison sources, either may be NULL, not both:
+ *   risk[n] (fp32, higher = earlier event): i is WORSE than j iff risk_i > risk_j, they TIE iff risk_i == risk_j. Exact fp32
+ *     comparisons: sksurv's tied_tol (1e-8 by default) is restated as 0;
+ *   surv[n, lds] (fp32, lds >= Q, 1 <= Q <= 4096) with col[n] (int32): column col[i] holds every sample's predicted probability of
+ *     surviving y_i. col[i] is read only where e_i = 1 and must lie in [0, Q) there (the caller's duty; a value outside is clamped, no
+ *     address outside a row is formed). i is WORSE than j iff surv[i, col[i]] < surv[j, col[i]], they TIE iff the two are equal.
+ * No NaN anywhere (the caller's duty). tau[T] (device, fp32, 1 <= T <= 8): truncation times, +inf = none.
+ * The pair (i, j), i the case, is COMPARABLE iff e_i = 1 and (y_j > y_i or (y_j == y_i and e_j = 0)) -- sksurv's _get_comparable and
+ * pycox's antolini rule. Per case i and row: Kcomp_i = sum_j w_j [comparable], Kconc_i = sum_j w_j [comparable][i worse than j],
+ * Ktied_i = sum_j w_j [comparable][i ties j]; exact integers below 2^31. Source s = 0 is risk, s = 1 is surv:
+ *   counts[r, s, 0..2] (int64) = sum_i w_i Kconc_i, sum_i w_i Ktied_i, sum_i w_i Kcomp_i over all cases. Exact. With surv: Antolini's
+ *     C_td = conc / comp, adjusted (conc + tied / 2) / comp; with risk: Harrell's C = (conc + tied / 2) / comp under these tie rules;
+ *   sums[r, s, t, 0..2] (double) = sum_{i: e_i = 1, y_i < tau[t], G(y_i) > 0} w_i G(y_i)^-2 (Kconc_i, Ktied_i, Kcomp_i): Uno's
+ *     C(tau) = (conc + tied / 2) / comp on these. G is the Kaplan-Meier estimate of the censoring distribution OF THE ROW as defined for
+ *     advmil_ipcw_rows (events before censorings at a tied time, right-continuous), at the sample's own time: the same bits;
+ *   rowcnt[r, 0..1+T] (int64) = sum w, sum w e, and per tau the weight of the cases with y_i < tau[t] whose G(y_i) == 0 (an event tied
+ *     with the censorings that end the row). Such cases are left out of the sums; a row with a non-zero count is UNDEFINED for that tau
+ *     (sksurv raises there), and so is a row with comp == 0.
+ *   The slots of an absent source are written as 0.
+ * Every output slot is written. A row's outputs depend on that row's inputs only (not on R, its position or what the buffers held); no
+ * atomics, a fixed order of every sum and product: the same bits from run to run.
+ * Error of a double sum, u = 2^-53: G(y_i) is a product of at most n factors, each the correctly rounded quotient of exact integers,
+ * joined by at most n - 1 rounded multiplications (a factor that is exactly 1 costs nothing): relative (2n - 1) u. A term squares it
+ * (2 (2n - 1) u + u), divides w_i by it (u) and multiplies by the exact K_i (u): relative (4n + 1) u. Adding at most n non-negative
+ * terms in any order costs (n - 1) u more: below 5 n u to first order, and with the second-order terms (5 n u < 4e-11) below
+ * 3 n 2^-52 relative. (conc + tied / 2) / comp of three such sums: relative 3 * 3 n 2^-52 at the most.
+ * ws: 8-byte aligned, >= advmil_concord_rows_workspace_bytes(n, R, T) (a pure host function: R n doubles for G, R ceil(n / 256)
+ * (5 + 6 T) 8-byte partial sums, n int32 rounded up to 8 bytes; 0 for a shape outside the limits), else ADVMIL_EWORKSPACE.
+ * 1 <= n <= 2^16, 1 <= R <= 2^20, 1 <= T <= 8, 4-byte (stime, sevent, order, weights, risk, surv, col, tau) and 8-byte (counts, rowcnt,
+ * sums, ws) alignment, else ADVMIL_EINVAL before anything is enqueued. Asynchronous on `stream`, capturable, no host synchronisation.
+ * advmil_concord_rows_plan: the walks' constants (pure host function): rows per workgroup and sorted samples per trip of the per-row walk,
+ * threads = cases per tile = controls per LDS tile of the pair pass, rows a pair-pass workgroup carries. */
+size_t advmil_concord_rows_workspace_bytes(int64_t n, int R, int T);
+int advmil_concord_rows(const float* stime, const float* sevent, const int32_t* order, int64_t n, const int32_t* weights, int64_t ldw, int R,
+                        const float* risk, const float* surv, int64_t lds, int Q, const int32_t* col, const float* tau, int T,
+                        int64_t* counts, int64_t* rowcnt, double* sums, void* ws, size_t ws_bytes, advmil_stream_t stream);
+int advmil_concord_rows_plan(int* walk_rows, int* walk_trip, int* pair_tile, int* pair_rows);
+
+/* ------------------------------------------------------------------------------------------
  * Survival evaluators (eval/evaluator.py:11,133,213) and the two O(n^2) pair losses (loss/utils.py:43-80, 155-175), csrc/survk.hip.
  * fp32 inputs; every term is formed in fp32 (exp / log of a term: the hardware v_exp_f32 / v_log_f32, ~1 ulp), every sum is carried
  * in double; per-anchor logs and the rescaling of the softmax merge are double-precision libm. No floating-point atomics: partials go
