@@ -241,6 +241,10 @@ SIGNATURES = {
     "advmil_concord_rows": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_int64, c_int,
                                     c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "advmil_concord_rows_plan": (c_int, [ctypes.POINTER(c_int), ctypes.POINTER(c_int), ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),
+    "advmil_calib_rows_workspace_bytes": (c_size_t, [c_int64, c_int, c_int]),
+    "advmil_calib_rows": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int, c_void_p, c_int64, c_int, c_void_p, c_int,
+                                  c_float, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "advmil_calib_rows_plan": (c_int, [ctypes.POINTER(c_int), ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),
     "advmil_surv_metrics_cont_workspace_bytes": (c_size_t, [c_int64]),
     "advmil_surv_metrics_cont": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_float, c_float, c_int, c_float, c_int, c_void_p,
                                          c_void_p, c_size_t, c_void_p]),

@@ -7,5 +7,6 @@ from .timedep import (bootstrap_timedep, brier_score, cumulative_dynamic_auc, de
                       statistics_from_rows, survival_from_hazards, survival_from_samples)
 from .concordance import (bootstrap_concordance, columns_at_own_times, concord_rows, concordance_ipcw, concordance_td,  # noqa: F401
                           surv_at_own_times)
+from .calibration import (bootstrap_calibration, calib_rows, d_calibration, survival_at_own_time, time_error)  # noqa: F401
 from .evaluator import ContSurv_Evaluator, DiscSurv_Evaluator, CoxSurv_Evaluator  # noqa: F401
 from .utils import prepare_evaluator  # noqa: F401

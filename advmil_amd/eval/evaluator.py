@@ -23,6 +23,7 @@ from .cindex import concordance_index, concordance_index_censored
 from .stratify import _risks, stratify_risk
 from . import timedep as TD
 from . import concordance as CC
+from . import calibration as CB
 
 _WHICH = {"bce": 0, "hinge": 1, "wasserstein": 2}
 # slots of the result array (doubles): [0, 16) the family's fused sums, [16, 20) rank_loss state, [20, 22) SurvPLE
@@ -86,6 +87,23 @@ def _fake_of(data, dev):
 
 def _mean(total, count):
     return total / count if count > 0 else float("nan")          # torch.mean of an empty selection
+
+
+def _calibration_dict(b, names, n_boot):
+    """The namespace of `bootstrap_calibration` as the dict the evaluators return: the statistics `names`, with `n_boot` > 0 their
+    intervals, the paired differences where there are two prediction columns, and `n_undefined`."""
+    out = {}
+    for k in names:
+        for key in (k, k + "_diff"):
+            if hasattr(b, key):
+                out[key] = getattr(b, key)
+                if n_boot > 0:
+                    out[key + "_lo"], out[key + "_hi"] = getattr(b, key + "_lo"), getattr(b, key + "_hi")
+    if hasattr(b, "d_cal_bins"):
+        out["d_cal_bins"] = b.d_cal_bins
+    if n_boot > 0:
+        out["n_undefined"] = b.n_undefined
+    return out
 
 
 class _Evaluator(object):
@@ -261,6 +279,37 @@ class ContSurv_Evaluator(_Evaluator):
                 out[m] = _mean(r[8], n_non)
         return out
 
+    def time_error(self, data, gamma=1.0, n_boot=0, seed=0, level=0.95):
+        """How wrong the predicted time is, with the censored patients' unknown event times replaced by Kaplan-Meier surrogates
+        (eval/calibration.py, one call): `mae_hinge` (at `gamma` = 1 the `mae` metric), `mae_margin` and `mae_po`, each [P]: column 0 is
+        the prediction the `c_index` metric uses, column 1 the median of `dist_y_hat` when the collector holds one -- then also
+        `<key>_diff`, column 0 - column 1. NaN where undefined; with `n_boot` > 0 the percentile intervals `<key>_lo` / `<key>_hi` at
+        `level` and `n_undefined` (more than 5 % of the resamples: ValueError)."""
+        dev = _device_of(data)
+        y = _f32(data["y"], dev)
+        t, e = y[:, 0].contiguous(), y[:, 1].contiguous()
+        pred = _f32(data["avg_y_hat"] if "avg_y_hat" in data else data["y_hat"], dev).reshape(-1, 1)
+        if data.get("dist_y_hat") is not None:
+            dist = _f32(data["dist_y_hat"], dev)
+            pred = torch.cat([pred, dist.reshape(dist.shape[0], -1).median(dim=1, keepdim=True).values], dim=1)
+        b = CB.bootstrap_calibration(e, t, pred=pred, gamma=gamma, n_boot=n_boot, seed=seed, level=level)
+        return _calibration_dict(b, ("mae_hinge", "mae_margin", "mae_po"), n_boot)
+
+    def d_calibration(self, data, bins=10, n_boot=0, seed=0, level=0.95):
+        """Is the sampled distribution `dist_y_hat` calibrated (eval/calibration.py, one call): the share of a patient's samples beyond
+        their own time is binned into `bins` bins, a censored patient spread over the bins below theirs; `d_cal_chi2`, its p-value
+        `d_cal_p` (small: miscalibrated) and the bin masses `d_cal_bins`; with `n_boot` > 0 the percentile intervals and `n_undefined`."""
+        if data.get("dist_y_hat") is None:
+            raise ValueError("d_calibration scores the predicted distribution: the collector holds no 'dist_y_hat' "
+                             "(run test_model with times_test_sample > 1)")
+        dev = _device_of(data)
+        y = _f32(data["y"], dev)
+        t, e = y[:, 0].contiguous(), y[:, 1].contiguous()
+        dist = _f32(data["dist_y_hat"], dev)
+        p = CB.survival_at_own_time(t, dist_y_hat=dist.reshape(dist.shape[0], -1))
+        b = CB.bootstrap_calibration(e, t, p_own=p, bins=bins, po=False, n_boot=n_boot, seed=seed, level=level)
+        return _calibration_dict(b, ("d_cal_chi2", "d_cal_p"), n_boot)
+
     def _survival_estimate(self, data, times):
         """The survival function is the empirical one of the generator's sampled times `dist_y_hat` [n, S, 1]; the risk at t is 1 - S(t)."""
         if data.get("dist_y_hat") is None:
@@ -374,6 +423,18 @@ class DiscSurv_Evaluator(_Evaluator):
         _lib.check(L.advmil_surv_metrics_disc(_p(hz), hz.stride(0), _p(t), _p(e), None, n, bins, 0.0, 1e-7, 0, _p(risk), _p(res), _p(ws), wsb,
                                               _stream(dev)), "surv_metrics_disc")
         return e, t, -risk
+
+    def d_calibration(self, data, bins=10, n_boot=0, seed=0, level=0.95):
+        """Are the predicted hazards calibrated (eval/calibration.py, one call): prod_{l <= k} (1 - h_l) at a patient's own bin k is
+        binned into `bins` bins, a censored patient spread over the bins below theirs; `d_cal_chi2`, its p-value `d_cal_p` (small:
+        miscalibrated) and the bin masses `d_cal_bins`; with `n_boot` > 0 the percentile intervals and `n_undefined`."""
+        dev = _device_of(data)
+        y = _f32(data["y"], dev)
+        t, e = y[:, 0].contiguous(), y[:, 1].contiguous()
+        hz = _f32(data["avg_y_hat"] if "avg_y_hat" in data else data["y_hat"], dev)
+        p = CB.survival_at_own_time(t, hazards=hz.reshape(hz.shape[0], -1))
+        b = CB.bootstrap_calibration(e, t, p_own=p, bins=bins, po=False, n_boot=n_boot, seed=seed, level=level)
+        return _calibration_dict(b, ("d_cal_chi2", "d_cal_p"), n_boot)
 
     def _survival_estimate(self, data, times):
         """The survival function is the product of the hazards' complements; times are bin indices (default: 0 ... bins - 2 below the

@@ -878,6 +878,74 @@ int advmil_concord_rows(const float* stime, const float* sevent, const int32_t* 
 int advmil_concord_rows_plan(int* walk_rows, int* walk_trip, int* pair_tile, int* pair_rows);
 
 /* ------------------------------------------------------------------------------------------
+ * Censoring-aware time error and D-calibration, csrc/calib.hip: how wrong a predicted TIME is when the censored samples' unknown event
+ * times are replaced by a surrogate built from the cohort's Kaplan-Meier curve (the margin and the pseudo-observation of Qi et al.,
+ * ICML 2023), next to the plain hinge (the reference's `mae`), and whether a predicted DISTRIBUTION is calibrated (D-calibration, Haider
+ * et al., JMLR 2020), for R rows of integer weights (bootstrap resamples) over one cohort of n samples. The tail convention (the curve is
+ * integrated to the row's largest time and no further) and the tie conventions below are THIS PROJECT'S; other packages extrapolate the
+ * tail differently. A weighted row is by definition the unweighted computation on the arrays in which sample i stands weights[r, i] times.
+ * The cohort is prepared as for advmil_concord_rows: order[n] (int32) = a stable ascending sort of the times, stime[k] = time[order[k]],
+ * sevent[k] = event[order[k]] (!= 0: observed). Everything else stays in the caller's sample order and is read through `order` (an entry
+ * outside [0, n) is read as 0): weights[R, ldw] (int32, >= 0, ldw >= n; NULL: all ones; every row sum < 2^31: the caller's duty).
+ * Two sources, either may be NULL, not both:
+ *   pred[n, ldp] (fp32, ldp >= P, 1 <= P <= 8): P columns of predicted times (the mean and the median of the samples, or two models);
+ *   p_own[n] (fp32 in [0, 1]): the predicted probability of surviving one's own time, S_i(t_i); binned into `bins` = B bins.
+ * 1 <= P <= 8 and 2 <= B <= 32 size the outputs and are checked whether or not the source is there. gamma (fp32, not NaN): the hinge
+ * margin. Times >= 0 and no NaN anywhere are the caller's duty.
+ * Per row: N = sum w; the distinct times with positive weight u_1 < ... < u_K, u_0 = 0; d_v = sum w e [t = u_v], n_v = sum w [t >= u_v].
+ *   S(u_v) = prod_{x <= v} (1 - d_x / n_x): the event Kaplan-Meier curve of the row, right-continuous, events before censorings at a
+ *     tie, 1 before u_1;
+ *   theta = sum_v S(u_{v-1}) (u_v - u_{v-1}): the restricted mean to the row's largest time; A(u_k) = sum_{v > k} S(u_{v-1}) (u_v - u_{v-1});
+ *   hinge, per column: sum_{e=1} w |t - y| + sum_{e=0} w max(0, t + gamma - y), over N. gamma = 1: the reference's `mae` (recon_loss at
+ *     its default gamma, cur_alpha = 0); gamma = 0: the textbook hinge;
+ *   margin: a censored sample of block k has the surrogate m = t + A(u_k) / S(u_k) (m = t where S(u_k) = 0) and the confidence
+ *     omega = 1 - S(u_k); an event has m = t, omega = 1. Numerator sum w omega |m - y|, denominator sum w omega;
+ *   pseudo-observation (only if with_po): for a censored sample of block k, theta^(-k) is the same restricted mean over the SAME grid
+ *     u_1 .. u_K with every n_v, v <= k, lowered by one (a factor whose lowered n_v is 0 is 1); it depends on the block only. The
+ *     surrogate is N theta - (N - 1) theta^(-k) -- what literally deleting one copy of the sample from the expanded arrays and
+ *     integrating the new curve over the full row's grid gives; omega, numerator and denominator as for the margin;
+ *   D-calibration: a sample's bin is k = min(B - 1, (int)(p * (float)B)), the product in fp32. An event adds w to bin k; a censored
+ *     sample with p > 0 adds w (p - k / B) / p to bin k and w / (B p) to every bin below it (in double, from the fp32 p); a censored
+ *     sample with p = 0 adds w to bin 0. The masses of a row sum to N.
+ * Outputs:
+ *   rowcnt[r, 0..3] (int64) = sum w, sum w e, K, the weight of the censored samples with S = 0 at their time. Exact. (Under these tie
+ *     conventions a censored sample is still counted in n_v at its own time, so d_v < n_v there and the last count is 0: it is the guard
+ *     of the `m = t where S = 0` clause, written so that a caller can see the clause was never taken);
+ *   km[r, 0..2]    (double) = theta, S(u_K), u_K (a row without weight: 0, 1, 0);
+ *   err[r, c, 0..2, 0..1] (double) = hinge, margin, pseudo-observation of column c, each numerator | denominator (the hinge's is N);
+ *   dcal[r, 0..B-1] (double) = the bin masses.
+ *   The slots of an absent source, and of the pseudo-observation when with_po == 0, are written as 0; with_po changes no other bit.
+ *   Margin and pseudo-observation are undefined where their denominator is 0 (a row without an event).
+ * Every output slot is written. A row's outputs depend on that row's inputs only (not on R, its position or what the buffers held); no
+ * atomics, a fixed order of every sum and product: the same bits from run to run.
+ * How theta^(-k) is formed: with g_v = (n_v - 1 - d_v) / (n_v - 1), S'_v = prod_{x <= v} g_x, theta'_k = sum_{v <= k} S'_{v-1}
+ * (u_v - u_{v-1}) and T_k = sum_{v > k} (prod_{k < x < v} (1 - d_x / n_x)) (u_v - u_{v-1}) = A(u_k) / S(u_k) (one backward recurrence),
+ * theta^(-k) = theta'_k + S'_k T_k: O(n) per row for all blocks together. A block of the cohort without weight in the row is a factor
+ * of exactly 1 and splits an interval in two: the row walks the cohort's blocks.
+ * Errors, u = 2^-53. Every factor is the correctly rounded quotient of exact integers; S, S' are products of at most n of them:
+ * relative (2n - 1) u. An interval is the difference of two fp32 times in double (u); theta, theta' add at most n non-negative terms
+ * S (u_v - u_{v-1}) ((2n + 1) u each, (n - 1) u for the sum in any order): relative 3 n u. T_k is a sum of non-negative products of
+ * at most n factors and an interval, formed by composing maps y -> a + f y: a term passes at most n multiplications and n additions,
+ * relative (3n + 1) u. All four: below 2 n 2^-52 relative. omega = 1 - S carries 2 n u ABSOLUTE; a term w omega |m - y| therefore an
+ * absolute error below (5n + 5) u w (m + |y|), and a numerator (hinge and margin) at most 5 n 2^-52 sum w (m + |gamma| + |y|), its
+ * denominator 2 n 2^-52 N. The pseudo-observation is N theta - (N - 1) theta^(-k), the difference of two numbers up to N u_K that are
+ * each relative 4 n 2^-52 at the most: ABSOLUTE 8 n 2^-52 N u_K per surrogate, and 2^-52 n (8 N u_K sum_{e=0} w + 5 sum w (|s| + |y|))
+ * for the numerator, s the surrogate. This loss of log2 N bits belongs to the DEFINITION of the pseudo-observation (it is there in
+ * exact deletion carried out in double just as well), not to the kernel. A D-calibration mass adds at most n terms of magnitude <= w
+ * (4 u w each) and at most B partial sums: ABSOLUTE (n + B + 4) 2^-52 N.
+ * ws: 8-byte aligned, >= advmil_calib_rows_workspace_bytes(n, R, with_po) (a pure host function: R n (3 + 2 with_po) doubles; 0 for a
+ * shape outside the limits), else ADVMIL_EWORKSPACE. 1 <= n <= 2^16, 1 <= R <= 2^20, with_po 0 or 1, 4-byte (stime, sevent, order,
+ * weights, pred, p_own) and 8-byte (rowcnt, km, err, dcal, ws) alignment, else ADVMIL_EINVAL before anything is enqueued. Asynchronous
+ * on `stream`, capturable, no host synchronisation.
+ * advmil_calib_rows_plan: the walks' constants (pure host function): rows per workgroup and sorted samples per trip of the per-row walk,
+ * rows per workgroup of the D-calibration pass. */
+size_t advmil_calib_rows_workspace_bytes(int64_t n, int R, int with_po);
+int advmil_calib_rows(const float* stime, const float* sevent, const int32_t* order, int64_t n, const int32_t* weights, int64_t ldw, int R,
+                      const float* pred, int64_t ldp, int P, const float* p_own, int bins, float gamma, int with_po, int64_t* rowcnt,
+                      double* km, double* err, double* dcal, void* ws, size_t ws_bytes, advmil_stream_t stream);
+int advmil_calib_rows_plan(int* walk_rows, int* walk_trip, int* dcal_rows);
+
+/* ------------------------------------------------------------------------------------------
  * Survival evaluators (eval/evaluator.py:11,133,213) and the two O(n^2) pair losses (loss/utils.py:43-80, 155-175), csrc/survk.hip.
  * fp32 inputs; every term is formed in fp32 (exp / log of a term: the hardware v_exp_f32 / v_log_f32, ~1 ulp), every sum is carried
  * in double; per-anchor logs and the rescaling of the softmax merge are double-precision libm. No floating-point atomics: partials go
